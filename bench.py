@@ -20,12 +20,19 @@ Workloads (BASELINE.json configs; the default is the headline one):
 value = units processed by all ranks / max-over-ranks wall time of the K timed steps
 (inputs already resident in HBM).  One process per GPU (torchrun), record-sharded with
 seed = base + rank: weak scaling.  `--gpus N` without a torchrun environment launches the N
-ranks itself (torch.distributed.run, 127.0.0.1) before anything touches the GPU.  Rank 0 prints ONE JSON line (contract: DESIGN.md
-§Measurement) carrying `roofline` for the dominant kernel (HIP-event timing on the engine's
-own stream, algorithmic bytes or ops per launch), `cpu_baseline` (the reference's own tools
-compiled from its sources, else the oracle/ C restatement, on a bounded sample, 1 core),
-`output_check` (the last step's output against the reference's digests) and `e2e` (the
-drop-in CLI end to end: file / pipe / warm context).
+ranks itself (torch.distributed.run, 127.0.0.1) before anything touches the GPU.  Rank 0 prints
+ONE JSON line (contract: DESIGN.md §Measurement).
+
+A plain run does what `value` needs and no more: generate and load the shard, W warmup steps,
+the K timed steps, the line (`ms_per_step` = the timed wall / K).  `--dump-outputs DIR` also
+writes what the last timed step computed (dump_outputs below); the inputs are a function of the
+arguments alone, so two builds can be compared output for output.  `--full` adds, as before:
+`roofline` for the dominant kernel and `kernels_ms` (the last warmup step profiled kernel by
+kernel, HIP events on the engine's own stream for the dominant one in the timed steps,
+algorithmic bytes or ops per launch), `output_check` (the last step's output against the
+reference's digests), `e2e` (the drop-in CLI end to end: file / pipe / warm context) and
+`cpu_baseline` (the reference's own tools compiled from its sources, else the oracle/ C
+restatement, on a bounded sample, 1 core).
 """
 import argparse
 import json
@@ -47,8 +54,13 @@ MFMA_FILE = os.path.join(REPO, "profiles", "r02_ld_mfma.json")  # tools/pmc_mfma
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 20; ld: 3)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel breakdown and roofline, the reference-digest check, the CPU baseline "
+                         "and the end-to-end CLI timings (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy")
     ap.add_argument("--workload", choices=("af", "pipeline", "ld", "nonref", "hwe", "dose", "ac", "md", "ph"), default="af")
     ap.add_argument("--records", type=int, default=None, help="records per GPU (default per workload)")
     ap.add_argument("--samples", type=int, default=2504)
@@ -68,8 +80,10 @@ def parse():
     a = ap.parse_args()
     if a.records is None:
         a.records = 100000 if a.workload == "ld" else 427409
-    if a.workload == "ld" and a.steps == 20:
-        a.steps = 3
+    if a.steps is None:
+        a.steps = 3 if a.workload == "ld" else 20
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     return a
 
 
@@ -545,6 +559,52 @@ def e2e_rates(workload, arr, a, offs=None):
         os.unlink(path)
 
 
+DUMP_TEXT_BYTES = 8 << 20   # output text kept per dump (32 MiB as float32, of the 64 MB a dump may take)
+DUMP_BLOCK = 64 << 10
+
+
+def dump_outputs(d, workload, eng, s):
+    """--dump-outputs: what the last timed step left for its caller, read back from the device as
+    the caller reads it, one DIR/<name>.npy each (float64 the counters and r^2, float32 the rest):
+      summary  the call's summary (n_lines, rows, data_lines, warn_lines, text_bytes, general_records;
+               ld: variants, pairs emitted, text_bytes)
+      text     the output text's byte values: whole up to 8 MiB, else 128 blocks of 64 KiB at fixed
+               (seeded) offsets, ascending
+      alt, tot, status   af: the per-line allele counts and status codes
+      status   pipeline / nonref: the per-line status codes (1 = kept)
+      ph_flags, ph_r2, ph_off   ph: the per-variant pair decisions, r^2 and entry offsets"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+
+    def put(name, arr, dt=np.float32):
+        np.save(os.path.join(d, name + ".npy"), np.asarray(arr).astype(dt))
+
+    if workload == "ld":
+        n_lines, tb = s[0], s[2]
+        put("summary", list(s), np.float64)
+    else:
+        n_lines, tb = s.n_lines, s.text_bytes
+        put("summary", [getattr(s, f) for f, _ in type(s)._fields_], np.float64)
+    if tb > DUMP_TEXT_BYTES:
+        n_blocks = DUMP_TEXT_BYTES // DUMP_BLOCK
+        offs = np.sort(np.random.default_rng(20251226).integers(0, tb - DUMP_BLOCK, n_blocks, endpoint=True))
+        put("text", np.concatenate([np.frombuffer(eng.text_range(int(o), DUMP_BLOCK), np.uint8) for o in offs]))
+    elif tb > 0:
+        put("text", np.frombuffer(eng.text_range(0, tb), np.uint8))
+    if workload == "af":
+        alt, tot, st = eng.lines(n_lines)
+        put("alt", alt)
+        put("tot", tot)
+        put("status", st)
+    elif workload in ("pipeline", "nonref"):
+        put("status", eng.statuses(n_lines))
+    elif workload == "ph":
+        flags, r2, off = eng.phaser_variants(s.rows)
+        put("ph_flags", flags)
+        put("ph_r2", r2, np.float64)
+        put("ph_off", off, np.float64)
+
+
 def launch_ranks(a):
     """`--gpus N` outside torchrun: start the N ranks as children (torch.distributed.run on
     127.0.0.1, one process per GPU) and return their exit code.  Nothing here has touched the
@@ -682,8 +742,10 @@ def main():
                       "ld_emit", "ld_count_sparse", "ld_count_mask", "ld_emit_mask", "ld_count_gen", "ld_emit_gen",
                       "ld_text")
 
+    # a plain run: W warmup steps, the K timed steps, the result line.  --full: the last warmup
+    # step is the profiled one, and the dominant kernel carries events in the timed steps
     s = None
-    for _ in range(max(a.warmup - 1, 0)):
+    for _ in range(max(a.warmup - 1, 0) if a.full else a.warmup):
         s = step()
 
     def stats():
@@ -698,7 +760,7 @@ def main():
     # the dominant kernel, the only one with HIP events in the timed steps (an event pair per
     # launch, read after the loop)
     kernels, dom_k = {}, None
-    if a.warmup > 0:
+    if a.full and a.warmup > 0:
         eng.set_profiling(True)
         eng.reset_kernel_stats()
         s = step()
@@ -711,17 +773,21 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    eng.set_profiling(True)
-    eng.reset_kernel_stats()
+    if a.full:
+        eng.set_profiling(True)
+        eng.reset_kernel_stats()
     barrier()
     t0 = time.perf_counter()
     for _ in range(a.steps):
         s = step()
     barrier()
     dt = time.perf_counter() - t0
-    eng.set_profiling(False)
-    eng.set_profiling_only(None)
-    kernels.update(stats())  # (the dominant kernel: its launches in the timed steps)
+    if a.full:
+        eng.set_profiling(False)
+        eng.set_profiling_only(None)
+        kernels.update(stats())  # (the dominant kernel: its launches in the timed steps)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs if rank == 0 else os.path.join(a.dump_outputs, "rank%d" % rank), a.workload, eng, s)
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda" if a.dist_backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -747,7 +813,9 @@ def main():
 
     if rank == 0:
         L = a.records
-        if ld:
+        if not a.full:
+            roof = None  # (no kernel carried events)
+        elif ld:
             # X.X^T over the window pairs (complete genotypes) on the FP4 MFMA: 2 ops per sample
             # per pair, priced against the dense FP4 peak the kernel's instruction runs at
             # the count kernel of the data: k_ld_fast (complete 256-groups, X.X^T) or, with
@@ -875,21 +943,22 @@ def main():
                        "bytes_per_gpu": int(arr.size),
                        "parallelism": "record-sharded x%d%s" % (world, ", RCCL all-reduce of global counts"
                                                                 if world > 1 else "")},
-            "roofline": roof,
-            "kernels_ms": kernels,
-            "kernels_ms_source": "%s: HIP events on the engine stream over the timed steps; the others: one "
-                                 "profiled warmup step" % (dom_k or "every kernel"),
             "pipeline_input_gbps": region_bytes * world * a.steps / dt / 1e9,
         }
         if ld:
             out["pairs_per_gpu"] = pairs
             out["pairs_emitted"] = np_
-        out["output_check"] = ({"checked": False, "match": None, "what": "--no-output-check (diagnostic run)"}
-                           if a.no_output_check else output_check(a.workload, eng, s, a, rank, arr))
-        if world == 1 and not a.no_e2e and not general:
-            out["e2e"] = e2e_rates(a.workload, arr, a, offs)
-        if world == 1 and not a.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(a.workload, arr, offs, a)
+        if a.full:
+            out["roofline"] = roof
+            out["kernels_ms"] = kernels
+            out["kernels_ms_source"] = ("%s: HIP events on the engine stream over the timed steps; the others: one "
+                                        "profiled warmup step" % (dom_k or "every kernel"))
+            out["output_check"] = ({"checked": False, "match": None, "what": "--no-output-check (diagnostic run)"}
+                                   if a.no_output_check else output_check(a.workload, eng, s, a, rank, arr))
+            if world == 1 and not a.no_e2e and not general:
+                out["e2e"] = e2e_rates(a.workload, arr, a, offs)
+            if world == 1 and not a.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(a.workload, arr, offs, a)
         print(json.dumps(out), flush=True)
     eng.close()
     if dist is not None:

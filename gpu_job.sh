@@ -44,7 +44,7 @@ for l in sys.stdin:
     tail -3 "gpurun_out/$name.log" | cut -c1-400
     return $rc
 }
-FAST="--no-cpu-baseline --no-e2e"
+FAST="--full --no-cpu-baseline --no-e2e"
 MODE=${1:-test}
 shift
 case "$MODE" in
@@ -57,7 +57,7 @@ smoke)
     step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
 bench)
     n=$1; shift
-    step bench_$n 600 python -u bench.py "$@" || exit $?
+    step bench_$n 600 python -u bench.py --full "$@" || exit $?
     grep '^{' gpurun_out/bench_$n.log | tail -1 > gpurun_out/bench_$n.json ;;
 ab)
     n=$1 lib=$2 k=$3; shift 3
@@ -90,7 +90,7 @@ mfma)
         SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE -d gpurun_out/pmc_${n}_mfma -o run --output-format csv -- \
         python bench.py --steps 2 --warmup 1 $FAST "$@" || exit $? ;;
 rehearse)
-    step rehearse_af 600 python bench.py --gpus 2 --steps 3 --warmup 1 --dist-backend gloo || exit $?
+    step rehearse_af 600 python bench.py --full --gpus 2 --steps 3 --warmup 1 --dist-backend gloo || exit $?
     grep '^{' gpurun_out/rehearse_af.log > gpurun_out/rehearse_af.json ;;
 run)
     n=$1 secs=$2; shift 2
