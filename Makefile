@@ -8,11 +8,11 @@ ARCH ?= gfx950
 B := build
 GPU_SRC := vcfx_amd/csrc/gpu
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Iinclude -I$(GPU_SRC) $(EXTRA_HIPFLAGS)
-GPU_OBJS := $(B)/obj/vcfxg_kernels.o $(B)/obj/vcfxg_rf.o $(B)/obj/vcfxg_ld.o $(B)/obj/vcfxg_ld_fast.o $(B)/obj/vcfxg_ld_mask.o $(B)/obj/vcfxg_af_walk.o $(B)/obj/vcfxg_fq_walk.o $(B)/obj/vcfxg_hwe.o $(B)/obj/vcfxg_dose.o $(B)/obj/vcfxg_md.o $(B)/obj/vcfxg_ac.o $(B)/obj/vcfxg_ph.o $(B)/obj/vcfxg_inflate.o $(B)/obj/vcfxg_api.o $(B)/obj/vcfxg_decimal.o
+GPU_OBJS := $(B)/obj/vcfxg_kernels.o $(B)/obj/vcfxg_rf.o $(B)/obj/vcfxg_ld.o $(B)/obj/vcfxg_ld_fast.o $(B)/obj/vcfxg_ld_mask.o $(B)/obj/vcfxg_af_walk.o $(B)/obj/vcfxg_fq_walk.o $(B)/obj/vcfxg_hwe.o $(B)/obj/vcfxg_dose.o $(B)/obj/vcfxg_md.o $(B)/obj/vcfxg_ac.o $(B)/obj/vcfxg_ph.o $(B)/obj/vcfxg_ib.o $(B)/obj/vcfxg_inflate.o $(B)/obj/vcfxg_api.o $(B)/obj/vcfxg_decimal.o
 
 TOOLS := VCFX_allele_freq_calc VCFX_genotype_query VCFX_record_filter VCFX_variant_counter VCFX_ld_calculator \
          VCFX_nonref_filter VCFX_hwe_tester VCFX_dosage_calculator VCFX_missing_detector VCFX_allele_counter \
-         VCFX_haplotype_phaser
+         VCFX_haplotype_phaser VCFX_inbreeding_calculator
 HOST_SRC := vcfx_amd/csrc/host
 TOOL_SRC := vcfx_amd/csrc/tools
 CXXFLAGS := -O2 -std=c++17 -fPIC -Wall -Wno-unused-result -Iinclude -I$(HOST_SRC) -I$(TOOL_SRC)
@@ -82,6 +82,12 @@ $(B)/bin/vcfx_bgzf: vcfx_amd/csrc/synth/vcfx_bgzf.c
 $(B)/bin/vcfx_drain: tools/microbench/pipe_drain.c
 	@mkdir -p $(dir $@)
 	$(CC) -O2 -o $@ $<
+
+# the dependent fp64 add latency of the device (not part of `all`: tools/ib_time.py builds it
+# on demand with `make build/bin/vcfx_dadd_latency`; the inbreeding chain's bound)
+$(B)/bin/vcfx_dadd_latency: tools/microbench/dadd_latency.hip
+	@mkdir -p $(dir $@)
+	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -o $@ $<
 
 # the drop-in's stdin reader with the device stage stubbed (the e2e leg's pipe ceiling)
 PIPE_CEIL_SRC := tools/microbench/pipe_ceiling.cpp tests/shard_tsan_stub.cpp $(HOST_SRC)/hostio.cpp $(HOST_SRC)/gz.cpp

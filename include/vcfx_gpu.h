@@ -324,6 +324,44 @@ typedef struct {
 int vcfxg_allele_counter(vcfxg_ctx *ctx, uint64_t first_line, uint64_t last_line, const vcfxg_ac_params *params,
                          vcfxg_summary *out);
 
+/* ---- VCFX_inbreeding_calculator (a row per SAMPLE, accumulated over every record) -----------
+ * Over the lines from data_start (the caller passes the end of the header lines it parsed): per
+ * record the genotype codes of parseGenotypeCode (VCFX_inbreeding_calculator.cpp:296-339: the GT
+ * prefix up to the first ':', "a/b" or "a|b" with anything after the second digit run ignored;
+ * 0/0 = 0, 0/1 = 1, 1/1 = 2, an allele above 1 or a '.' = -1), then per sample, in record order,
+ *   sumExp += 2 freq (1 - freq), obsHet += (code == 1), usedCount++
+ * with freq = (altSum - code) / (2 (nGood - 1)) (freq_mode 0, excludeSample) or altSum /
+ * (2 nGood) (freq_mode 1, global); skip_boundary drops freq <= 0 or >= 1, and
+ * count_boundary_as_used still counts such a record in usedCount (:596-626).  sumExp is the
+ * reference's fp64 sum bit for bit: the same operands added in the same order.
+ * mode VCFXG_MODE_FILE = calculateInbreedingMmap (:536-629): '\r' stripped, empty / '#' lines,
+ * an empty ALT, an ALT with a comma and lines without a tenth field skipped; only the sample
+ * columns that start before the line end are parsed, and a sample past them keeps the code of
+ * the last parsed record (the reused genotypeCodes buffer, zeros at first).  VCFXG_MODE_STDIN =
+ * calculateInbreedingStdin (:689-777): lines of fewer than 10 fields and an ALT with a comma
+ * skipped, a sample without a column is -1.  A record is used when at least two codes are >= 0.
+ * The text (vcfxg_fetch_text) holds one row per sample, "<name>\tNA\n", "<name>\t1.000000\n" or
+ * "<name>\t<F>\n" with F = 1 - obsHet / sumExp in appendDouble's digits (:230-266, :645-663),
+ * without the column header.  rows = used records, data_lines = parsed records,
+ * general_records = parsed records off the fixed-stride sweep, n_lines = lines from data_start.
+ * The records are processed in blocks of VCFXG_IB_BLOCK lines (read by vcfxg_open; default
+ * 65536; on the walk schedule rounded to whole walkers, at least one) with the per-sample state
+ * kept on the device; the schedule follows VCFXG_AF_FUSED (7 the walk, 3 / 8 the line index) and
+ * VCFXG_WALK_CHUNK as the other region calls do. */
+typedef struct {
+    uint32_t n_samples;          /* the header's sample count (> 0) */
+    const char *names;           /* the sample names, concatenated */
+    const uint64_t *name_off;    /* n_samples + 1 offsets into names */
+    int freq_mode;               /* 0 excludeSample, 1 global */
+    int skip_boundary;           /* --skip-boundary */
+    int count_boundary_as_used;  /* --count-boundary-as-used */
+} vcfxg_ib_params;
+int vcfxg_inbreeding_region(vcfxg_ctx *ctx, size_t data_start, int mode, const vcfxg_ib_params *params,
+                            vcfxg_summary *out);
+/* the last vcfxg_inbreeding_region call's per-sample accumulators (n_samples each; any may be
+ * NULL): sumExp, obsHet and usedCount of :527-529 */
+int vcfxg_inbreeding_samples(vcfxg_ctx *ctx, double *sum_exp, uint64_t *obs_het, uint64_t *used);
+
 /* ---- VCFX_haplotype_phaser (LD reuse in block phasing) ------------------
  * Over the lines from data_start (the byte after the '#CHROM' line): per line status 1 variant,
  * 4 '#' line, 3 "<10 fields", 7 invalid POS, 8 no GT in FORMAT, 0 empty (mode VCFXG_MODE_FILE:

@@ -19,6 +19,8 @@
  *   vcfx_tool_allele_counter    parseArguments/main, VCFX_allele_counter.cpp:352-395, 1473-1536
  *   vcfx_tool_haplotype_phaser  run/main, VCFX_haplotype_phaser.cpp:478-569, 1336-1342
  *   vcfx_tool_variant_counter   run, VCFX_variant_counter.cpp:154-218
+ *   VCFX_inbreeding_calculator  run/main, VCFX_inbreeding_calculator.cpp:855-905: by name through
+ *                               vcfx_tool_main and as an executable (no entry of its own here)
  *   vcfx_tool_main              the `vcfx <tool> ...` dispatch (src/vcfx_wrapper/vcfx.cpp:177-187)
  * Without a usable gfx950 device a tool that reaches the record loop writes
  * "no usable MI355X" to err_fd and returns 1 (no CPU fallback).

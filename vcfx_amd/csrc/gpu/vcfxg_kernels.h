@@ -263,4 +263,36 @@ hipError_t launch_af_format(const char *buf, int64_t data_start, const uint64_t 
                             const uint32_t *rowpre, const uint8_t *status, const uint64_t *off, char *out,
                             hipStream_t s, uint64_t text_cap = ~0ull);
 
+// VCFX_inbreeding_calculator (vcfxg_ib.hip).  Stage A fills, per slot, a meta record
+// (ib_meta_bytes(): status 0 skipped / 1 parsed / 2 used, altSum, nGood, nparsed) and a row of
+// ld int8 codes: launch_ib_walk with G walkers (chunks w0 .. w0 + G of nw over [lo, hi)), walker
+// g's lines in slots [g cap_w, g cap_w + cnt[g]), *ovf set when a walker has more lines than
+// cap_w; or launch_ib_lines over indexed lines [l0, l0 + n) (one group: cnt[0] = n, cap_w >= n).
+// counters [0] parsed records, [1] used records.  Stage B (launch_ib_table): offs = the scan of
+// cnt (G + 1 entries, offs[G] = the block's records) and, in file order, one record entry
+// (ib_rec_bytes()) per line: status, nparsed, slot, and for a used record the sumExp term of a
+// sample of code 0 / 1 / 2 with the boundary flag bits.  Stage C (launch_ib_chain): a lane per
+// sample over the block's n_rec[0] record entries (codes regrouped by launch_ib_pack), the per-sample state (sum_exp, obs_het, used,
+// carried code) read and written back.  launch_ib_rows: the rows.
+size_t ib_meta_bytes();
+size_t ib_rec_bytes();
+hipError_t launch_ib_walk(const char *buf, int64_t lo, int64_t hi, int64_t chunk, int64_t w0, int64_t nw, uint32_t G,
+                          uint32_t cap_w, int mode, uint32_t ns, uint32_t ld, int8_t *codes, void *meta, uint32_t *cnt,
+                          unsigned *ovf, unsigned long long *counters, hipStream_t s);
+hipError_t launch_ib_lines(const char *buf, int64_t data_start, const uint64_t *line_end, uint64_t l0, uint32_t n,
+                           int mode, uint32_t ns, uint32_t ld, int8_t *codes, void *meta, uint32_t *cnt,
+                           unsigned long long *counters, hipStream_t s);
+hipError_t launch_ib_table(const void *meta, const uint32_t *cnt, uint32_t *offs, uint32_t G, uint32_t cap_w,
+                           int global_freq, void *rec, hipStream_t s);
+// (slots: the block's slot capacity; packed: ib_packed_bytes(slots, ns) bytes, the codes regrouped
+// per 64-sample tile and 16 records; rec needs room for slots + 16 entries)
+size_t ib_packed_bytes(uint64_t slots, uint32_t ns);
+hipError_t launch_ib_pack(const int8_t *codes, uint32_t ld, const void *rec, const uint32_t *n_rec, uint64_t slots,
+                          void *packed, uint32_t ns, hipStream_t s);
+hipError_t launch_ib_chain(const void *rec, const uint32_t *n_rec, uint64_t slots, const void *packed, uint32_t ns,
+                           int mode, int skip_boundary, int count_boundary, double *sum_exp, uint64_t *obs_het,
+                           uint64_t *used, int32_t *carried, hipStream_t s);
+hipError_t launch_ib_rows(const double *sum_exp, const uint64_t *obs_het, const uint64_t *used, uint32_t ns,
+                          const char *names, const uint64_t *noff, char *out, uint64_t *text_bytes, hipStream_t s);
+
 }  // namespace vcfxg

@@ -15,6 +15,10 @@
 
 #include "vcfx_tools.h"
 
+// VCFX_inbreeding_calculator's entry (run/main, VCFX_inbreeding_calculator.cpp:855-905); reached
+// through vcfx_tool_main and the executable
+extern "C" int vcfx_tool_inbreeding_calculator(int argc, char **argv, int in_fd, int out_fd, int err_fd);
+
 namespace vcfxh {
 
 // compiled record_filter criterion (FilterCriterion, VCFX_record_filter.h:37-44)

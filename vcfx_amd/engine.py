@@ -22,6 +22,12 @@ class AcParams(ctypes.Structure):
                 ("name_off", ctypes.c_void_p), ("seq", ctypes.c_int), ("kind", ctypes.c_int)]
 
 
+class IbParams(ctypes.Structure):
+    _fields_ = [("n_samples", ctypes.c_uint32), ("names", ctypes.c_char_p), ("name_off", ctypes.c_void_p),
+                ("freq_mode", ctypes.c_int), ("skip_boundary", ctypes.c_int),
+                ("count_boundary_as_used", ctypes.c_int)]
+
+
 class Criterion(ctypes.Structure):
     _fields_ = [("target", ctypes.c_int), ("op", ctypes.c_int), ("numeric", ctypes.c_int), ("value", ctypes.c_double),
                 ("key", ctypes.c_char_p), ("key_len", ctypes.c_size_t), ("str", ctypes.c_char_p),
@@ -73,6 +79,8 @@ SIGNATURES = {
     "vcfxg_dosage_region": (_I, [_VP, _S, _I, ctypes.POINTER(Summary)]),
     "vcfxg_missing_region": (_I, [_VP, _S, _I, ctypes.POINTER(Summary)]),
     "vcfxg_allele_counter": (_I, [_VP, _U64, _U64, _VP, ctypes.POINTER(Summary)]),
+    "vcfxg_inbreeding_region": (_I, [_VP, _S, _I, _VP, ctypes.POINTER(Summary)]),
+    "vcfxg_inbreeding_samples": (_I, [_VP, _VP, _VP, _VP]),
     "vcfxg_fetch_text_range": (_I, [_VP, _U64, _S, _VP]),
     "vcfxg_shard_cuts": (_I, [_VP, _S, _S, _I, _VP]),
     "vcfxg_comm_init": (_I, [_VP, _I, ctypes.POINTER(_VP)]),
@@ -297,6 +305,34 @@ class Engine:
         s = Summary()
         self._chk(self.L.vcfxg_allele_counter(self.h, l0, l1, ctypes.byref(p), ctypes.byref(s)), "allele_counter")
         return s
+
+    def inbreeding_region(self, data_start, mode, names, freq_mode=0, skip_boundary=False,
+                          count_boundary_as_used=False):
+        """VCFX_inbreeding_calculator over the records from data_start: a row per sample (names:
+        the header's sample names; freq_mode 0 excludeSample / 1 global) (vcfxg_inbreeding_region)"""
+        import numpy as np
+        nb = [x.encode() if isinstance(x, str) else bytes(x) for x in names]
+        off = np.zeros(len(nb) + 1, np.uint64)
+        off[1:] = np.cumsum([len(x) for x in nb])
+        p = IbParams(len(nb), b"".join(nb), off.ctypes.data, int(freq_mode), int(skip_boundary),
+                     int(count_boundary_as_used))
+        s = Summary()
+        self._ib_n = 0
+        self._chk(self.L.vcfxg_inbreeding_region(self.h, data_start, int(mode), ctypes.byref(p), ctypes.byref(s)),
+                  "inbreeding_region")
+        self._ib_n = len(nb)
+        return s
+
+    def inbreeding_samples(self):
+        """(sum_exp float64, obs_het uint64, used uint64) per sample of the last inbreeding_region"""
+        import numpy as np
+        n = getattr(self, "_ib_n", 0)
+        if not n:
+            raise EngineError("inbreeding_samples: no successful inbreeding_region call on this context")
+        se, oh, us = np.zeros(n, np.float64), np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        self._chk(self.L.vcfxg_inbreeding_samples(self.h, se.ctypes.data, oh.ctypes.data, us.ctypes.data),
+                  "inbreeding_samples")
+        return se, oh, us
 
     def haplotype_phaser(self, data_start, mode, threshold, n_samples):
         """VCFX_haplotype_phaser's parse + consecutive-variant LD (vcfxg_haplotype_phaser)"""
