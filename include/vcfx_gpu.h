@@ -362,6 +362,50 @@ int vcfxg_inbreeding_region(vcfxg_ctx *ctx, size_t data_start, int mode, const v
  * NULL): sumExp, obsHet and usedCount of :527-529 */
 int vcfxg_inbreeding_samples(vcfxg_ctx *ctx, double *sum_exp, uint64_t *obs_het, uint64_t *used);
 
+/* ---- VCFX_sample_extractor (a text rewrite: the kept columns of every line) -------------------
+ * Over the indexed lines [first_line, last_line), at most VCFXG_SX_BLOCK of them a call (read by
+ * vcfxg_open; default 65536): the call takes the lines [first_line, first_line + n_lines) and the
+ * caller goes on from there, so the device text stays bounded (a line is at most its own bytes +
+ * 2 m + 1).  Number a line's fields from 0 and give a tab the number of the field it precedes: a
+ * written line is its bytes numbered 0..8 and those numbered cols[i], "\t." for every cols[i] the
+ * line has no field for, and '\n' (extractSamplesMmap, VCFX_sample_extractor.cpp:287-332;
+ * extractSamples :512-533).  Per line status (vcfxg_fetch_lines) and text (vcfxg_fetch_text /
+ * vcfxg_fetch_text_range, in line order):
+ *   VCFXG_SX_EMPTY      an empty line: "\n" (:216-220, :461-464)
+ *   VCFXG_SX_HEADER     a '#' line, copied (:271-275, :497-500)
+ *   VCFXG_SX_ROW        a data line, written as above
+ *   VCFXG_SX_SHORT      fewer than 8 fields: nothing; "line has <8 columns" (:311-315, :513-516)
+ *   VCFXG_SX_NO_SAMPLES stdin mode, exactly 8 fields: nothing; "data line with no sample columns"
+ *                       (:517-520; file mode writes the 8 fields and "\t." per kept column)
+ *   VCFXG_SX_PRE        a data line and seen_chrom == 0: nothing; "data line encountered before
+ *                       #CHROM" (:281-285, :508-511)
+ *   VCFXG_SX_CHROM      stdin mode, a line that starts with "#CHROM": nothing.  The reference
+ *                       selects again there (:466-496): the caller splits its range at such a line,
+ *                       writes the line itself and goes on with the new columns.  (File mode
+ *                       rewrites only the first one, :224, which the caller handles before the
+ *                       range; a later one is a VCFXG_SX_HEADER line.)
+ * mode VCFXG_MODE_FILE strips one trailing '\r' from every line first (:212-214), VCFXG_MODE_STDIN
+ * none, so there the '\r' belongs to the last field and stays only when that column is kept.
+ * cols: the kept columns' field numbers (>= 9), ascending; m = 0 is legal (fields 0..8 only).
+ * rows = lines written (VCFXG_SX_ROW), data_lines = non-empty lines that are not '#' lines,
+ * warn_lines = lines the caller has to act on (SHORT, NO_SAMPLES, PRE and CHROM), text_bytes,
+ * n_lines = the lines taken by this call. */
+#define VCFXG_SX_EMPTY 0
+#define VCFXG_SX_ROW 1
+#define VCFXG_SX_SHORT 3
+#define VCFXG_SX_HEADER 4
+#define VCFXG_SX_NO_SAMPLES 5
+#define VCFXG_SX_PRE 6
+#define VCFXG_SX_CHROM 7
+typedef struct {
+    const uint32_t *cols; /* kept columns: field numbers >= 9, strictly ascending */
+    uint64_t m;           /* their count (0: none) */
+    int mode;             /* VCFXG_MODE_FILE / VCFXG_MODE_STDIN */
+    int seen_chrom;       /* a '#CHROM' line precedes first_line */
+} vcfxg_sx_params;
+int vcfxg_sample_extract(vcfxg_ctx *ctx, uint64_t first_line, uint64_t last_line, const vcfxg_sx_params *params,
+                         vcfxg_summary *out);
+
 /* ---- VCFX_haplotype_phaser (LD reuse in block phasing) ------------------
  * Over the lines from data_start (the byte after the '#CHROM' line): per line status 1 variant,
  * 4 '#' line, 3 "<10 fields", 7 invalid POS, 8 no GT in FORMAT, 0 empty (mode VCFXG_MODE_FILE:

@@ -21,6 +21,7 @@
  *   vcfx_tool_variant_counter   run, VCFX_variant_counter.cpp:154-218
  *   VCFX_inbreeding_calculator  run/main, VCFX_inbreeding_calculator.cpp:855-905: by name through
  *                               vcfx_tool_main and as an executable (no entry of its own here)
+ *   vcfx_tool_sample_extractor  run/main, VCFX_sample_extractor.cpp:344-413, 554-560
  *   vcfx_tool_main              the `vcfx <tool> ...` dispatch (src/vcfx_wrapper/vcfx.cpp:177-187)
  * Without a usable gfx950 device a tool that reaches the record loop writes
  * "no usable MI355X" to err_fd and returns 1 (no CPU fallback).
@@ -44,12 +45,15 @@ int vcfx_tool_dosage_calculator(int argc, char **argv, int in_fd, int out_fd, in
 int vcfx_tool_missing_detector(int argc, char **argv, int in_fd, int out_fd, int err_fd);
 int vcfx_tool_allele_counter(int argc, char **argv, int in_fd, int out_fd, int err_fd);
 int vcfx_tool_haplotype_phaser(int argc, char **argv, int in_fd, int out_fd, int err_fd);
+/* the same signature as a type; entries added since are declared through it */
+typedef int vcfx_entry_fn(int argc, char **argv, int in_fd, int out_fd, int err_fd);
+vcfx_entry_fn vcfx_tool_sample_extractor;
 /* tool = "VCFX_<name>" (a leading path is ignored); -100 for an unknown tool */
 int vcfx_tool_main(const char *tool, int argc, char **argv, int in_fd, int out_fd, int err_fd);
 /* The same invocation over ngpu device contexts in this process (one host thread per rank;
  * SURVEY 8(b) vcfxg_shard_run, 8(e)): the record tools (allele_freq_calc, record_filter,
  * genotype_query, nonref_filter, dosage_calculator, hwe_tester, missing_detector,
- * allele_counter) on a file input run each rank on its record range of the file, cut at
+ * allele_counter, sample_extractor) on a file input run each rank on its record range of the file, cut at
  * i*size/ngpu and advanced past the next '\n' (VCFX_allele_counter.cpp:889-901);
  * ld_calculator (streaming) on its share of the pair rows.  Output bytes, stderr text and exit
  * code are those of the single-context run; global counts are all-reduced over the rank clique

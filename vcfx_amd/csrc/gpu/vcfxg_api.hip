@@ -129,6 +129,13 @@ struct vcfxg_ctx {
     // per-sample state carried from block to block (sumExp, obsHet, usedCount, carried code)
     DevBuf ib_codes, ib_meta, ib_tab, ib_packed, ib_cnt, ib_offs, ib_sum, ib_obs, ib_used, ib_carried, ib_small;
     uint32_t ib_ns = 0;  // samples of the last vcfxg_inbreeding_region call (0: none yet)
+    // VCFX_sample_extractor: the kept-field bitmask; lines per call (read when the context opens;
+    // tests make many blocks, and blocks of one line, with small values)
+    DevBuf sx_mask;
+    std::vector<uint32_t> sx_mask_host;
+    uint64_t sx_block = getenv("VCFXG_SX_BLOCK")
+                            ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_SX_BLOCK"), nullptr, 10), 1), 1u << 24)
+                            : 65536;
     // records per chain block (read when the context opens; tests cross block edges with 1, 7, 64)
     uint64_t ib_block = getenv("VCFXG_IB_BLOCK")
                             ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_IB_BLOCK"), nullptr, 10), 1), 1u << 24)
@@ -355,7 +362,7 @@ void vcfxg_close(vcfxg_ctx *c) {
     for (DevBuf *b : {&c->input, &c->idx_counts, &c->idx_offs, &c->idx_pos, &c->line_end, &c->d_nlines, &c->scan_tmp, &c->alt,
                       &c->tot, &c->rowpre, &c->status, &c->rowlen, &c->rowoff, &c->text, &c->counters, &c->query, &c->crit, &c->pool, &c->ld_G, &c->ld_lines,
                       &c->ld_vidx, &c->ld_valid, &c->ld_Gc, &c->ld_wcnt, &c->ld_wval, &c->ld_vbase, &c->ld_small, &c->ld_pend, &c->ld_vars, &c->ld_plen, &c->ld_poff, &c->ld_prefix,
-                      &c->ld_cid, &c->ld_blocks, &c->ld_cnt, &c->ld_off, &c->ld_pairs, &c->ld_fast, &c->ld_gflag, &c->ld_Gp, &c->ld_Gv, &c->ld_Gq, &c->dose_meta, &c->af_meta, &c->ld_temp, &c->ld_quarters, &c->ld_stage_ctr, &c->ld_rowoff, &c->async_small, &c->wk_le, &c->wk_alt, &c->wk_tot, &c->wk_rowpre, &c->wk_status, &c->wk_meta, &c->wk_count, &c->wk_offs, &c->wk_gt, &c->wk_small, &c->wk_tabs, &c->rf_tabs, &c->hwe_aux, &c->wk_aux, &c->hwe_rc, &c->wk_text, &c->wk_toff, &c->wk_start, &c->wk_cx, &c->wk_bs, &c->scratch_small, &c->byte_cnt, &c->ld_moff, &c->ld_midx, &c->ld_mvar, &c->ld_gt16, &c->ld_sprec, &c->ld_midx16, &c->bgz_in, &c->bgz_mem, &c->bgz_off, &c->bgz_stat, &c->bgz_small, &c->bgz_perm, &c->ib_codes, &c->ib_meta, &c->ib_tab, &c->ib_packed, &c->ib_cnt, &c->ib_offs, &c->ib_sum, &c->ib_obs, &c->ib_used, &c->ib_carried, &c->ib_small})
+                      &c->ld_cid, &c->ld_blocks, &c->ld_cnt, &c->ld_off, &c->ld_pairs, &c->ld_fast, &c->ld_gflag, &c->ld_Gp, &c->ld_Gv, &c->ld_Gq, &c->dose_meta, &c->af_meta, &c->ld_temp, &c->ld_quarters, &c->ld_stage_ctr, &c->ld_rowoff, &c->async_small, &c->wk_le, &c->wk_alt, &c->wk_tot, &c->wk_rowpre, &c->wk_status, &c->wk_meta, &c->wk_count, &c->wk_offs, &c->wk_gt, &c->wk_small, &c->wk_tabs, &c->rf_tabs, &c->hwe_aux, &c->wk_aux, &c->hwe_rc, &c->wk_text, &c->wk_toff, &c->wk_start, &c->wk_cx, &c->wk_bs, &c->scratch_small, &c->byte_cnt, &c->ld_moff, &c->ld_midx, &c->ld_mvar, &c->ld_gt16, &c->ld_sprec, &c->ld_midx16, &c->bgz_in, &c->bgz_mem, &c->bgz_off, &c->bgz_stat, &c->bgz_small, &c->bgz_perm, &c->ib_codes, &c->ib_meta, &c->ib_tab, &c->ib_packed, &c->ib_cnt, &c->ib_offs, &c->ib_sum, &c->ib_obs, &c->ib_used, &c->ib_carried, &c->ib_small, &c->sx_mask})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : c->bgz_tok)
         if (b.p) (void)hipFree(b.p);
@@ -2448,6 +2455,77 @@ int vcfxg_allele_counter(vcfxg_ctx *c, uint64_t l0, uint64_t l1, const vcfxg_ac_
         out->data_lines = tail[2];
         out->warn_lines = tail[3];
         out->general_records = tail[4];
+        out->text_bytes = text;
+    }
+    return VCFXG_OK;
+}
+
+static_assert(vcfxg::kSxEmpty == VCFXG_SX_EMPTY && vcfxg::kSxRow == VCFXG_SX_ROW && vcfxg::kSxShort == VCFXG_SX_SHORT &&
+                  vcfxg::kSxHeader == VCFXG_SX_HEADER && vcfxg::kSxNoSample == VCFXG_SX_NO_SAMPLES &&
+                  vcfxg::kSxPre == VCFXG_SX_PRE && vcfxg::kSxChrom == VCFXG_SX_CHROM,
+              "sample_extract line statuses");
+// VCFX_sample_extractor over indexed lines [l0, min(l1, l0 + sx_block)): statuses and output bytes,
+// a scan, the bytes (one host synchronisation for the text size)
+int vcfxg_sample_extract(vcfxg_ctx *c, uint64_t l0, uint64_t l1, const vcfxg_sx_params *p, vcfxg_summary *out) {
+    if (!c || !p || (p->m && !p->cols) || p->m >= (1ull << 31) ||
+        (p->mode != VCFXG_MODE_FILE && p->mode != VCFXG_MODE_STDIN))
+        return VCFXG_E_ARG;
+    if (!c->indexed) return VCFXG_E_STATE;
+    DENSE(c);
+    if (l0 > l1 || l1 > c->n_lines) return VCFXG_E_ARG;
+    l1 = std::min(l1, l0 + c->sx_block);
+    for (uint64_t i = 0; i < p->m; i++)  // field numbers past FORMAT, ascending
+        if (p->cols[i] < 9 || p->cols[i] >= (1u << 31) || (i && p->cols[i] <= p->cols[i - 1])) return VCFXG_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t n = l1 - l0, L = c->n_lines;
+    const uint32_t m = (uint32_t)p->m, lastk = m ? p->cols[m - 1] : 8u, nwords = lastk / 32u + 1u;
+    c->sx_mask_host.assign((size_t)nwords + 2, 0u);
+    c->sx_mask_host[0] = 0x1FFu;
+    for (uint32_t i = 0; i < m; i++) c->sx_mask_host[p->cols[i] >> 5] |= 1u << (p->cols[i] & 31u);
+    int r = ensure(c, c->sx_mask, 4 * ((size_t)nwords + 2));
+    if (!r) r = af_buffers(c, L);
+    if (r) return r;
+    HIPCHK(c, hipMemcpyAsync(c->sx_mask.p, c->sx_mask_host.data(), 4 * ((size_t)nwords + 2), hipMemcpyHostToDevice,
+                             c->stream));
+    HIPCHK(c, hipMemsetAsync(c->counters.p, 0, 64, c->stream));
+    HIPCHK(c, hipMemsetAsync(P<uint64_t>(c->rowlen) + n, 0, 8, c->stream));
+    const uint64_t wpb = (uint64_t)(vcfxg::sx_threads() / 64);
+    const unsigned blocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + wpb - 1) / wpb, 8192));
+    const char *buf = P<char>(c->input);
+    const int stdin_mode = p->mode == VCFXG_MODE_STDIN, seen = p->seen_chrom ? 1 : 0;
+    prof_begin(c, "sx_len");
+    HIPCHK(c, vcfxg::launch_sx_len(buf, (int64_t)c->data_start, P<uint64_t>(c->line_end), l0, l1, blocks,
+                                   P<uint32_t>(c->sx_mask), nwords, lastk, m, stdin_mode, seen, P<uint8_t>(c->status),
+                                   P<uint64_t>(c->rowlen), P<unsigned long long>(c->counters), c->stream));
+    prof_end(c, "sx_len");
+    prof_begin(c, "sx_scan");
+    r = exclusive_scan(c, P<uint64_t>(c->rowlen), P<uint64_t>(c->rowoff), (size_t)n + 1);
+    prof_end(c, "sx_scan");
+    if (r) return r;
+    static thread_local uint64_t tail[5];
+    HIPCHK(c, hipMemcpyAsync(&tail[0], P<uint64_t>(c->rowoff) + n, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&tail[1], c->counters.p, 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const uint64_t text = n ? tail[0] : 0;
+    c->text_bytes = 0;
+    r = ensure(c, c->text, text + 16);
+    if (r) return r;
+    prof_begin(c, "sx_write");
+    HIPCHK(c, vcfxg::launch_sx_write(buf, (int64_t)c->data_start, P<uint64_t>(c->line_end), l0, l1, blocks,
+                                     P<uint32_t>(c->sx_mask), nwords, lastk, m, stdin_mode, seen, P<uint8_t>(c->status),
+                                     P<uint64_t>(c->rowoff), P<char>(c->text), c->stream));
+    prof_end(c, "sx_write");
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    c->text_bytes = text;
+    if (out) {
+        std::memset(out, 0, sizeof *out);
+        out->n_lines = n;
+        if (n) {
+            out->rows = tail[1];
+            out->data_lines = tail[2];
+            out->warn_lines = tail[3] + tail[4];
+        }
         out->text_bytes = text;
     }
     return VCFXG_OK;

@@ -295,4 +295,23 @@ hipError_t launch_ib_chain(const void *rec, const uint32_t *n_rec, uint64_t slot
 hipError_t launch_ib_rows(const double *sum_exp, const uint64_t *obs_het, const uint64_t *used, uint32_t ns,
                           const char *names, const uint64_t *noff, char *out, uint64_t *text_bytes, hipStream_t s);
 
+// VCFX_sample_extractor (vcfxg_sx.hip) over indexed lines [l0, l1), a wave per line.  mask:
+// nwords + 2 words, bit f = field f of a line is kept (bits 0..8 set; the last two words zero),
+// lastk the largest kept field number (8 without a kept column), m the kept columns.
+// launch_sx_len: per line its status (kSx*) and output bytes (len[li - l0]); counters [0] lines
+// written, [1] data lines, [2] skipped data lines, [3] '#CHROM' lines (stdin mode).
+// launch_sx_write: the lines' bytes at off[li - l0] (the scan of len, l1 - l0 + 1 entries) of out
+// (16 B aligned).  A line passes through a ring of sx_stage_bytes() per wave, drained every 1 KiB.
+enum : uint8_t { kSxEmpty = 0, kSxRow = 1, kSxShort = 3, kSxHeader = 4, kSxNoSample = 5, kSxPre = 6, kSxChrom = 7 };
+int sx_threads();
+uint32_t sx_stage_bytes();
+hipError_t launch_sx_len(const char *buf, int64_t data_start, const uint64_t *line_end, uint64_t l0, uint64_t l1,
+                         unsigned blocks, const uint32_t *mask, uint32_t nwords, uint32_t lastk, uint32_t m,
+                         int stdin_mode, int seen, uint8_t *status, uint64_t *len, unsigned long long *counters,
+                         hipStream_t s);
+hipError_t launch_sx_write(const char *buf, int64_t data_start, const uint64_t *line_end, uint64_t l0, uint64_t l1,
+                           unsigned blocks, const uint32_t *mask, uint32_t nwords, uint32_t lastk, uint32_t m,
+                           int stdin_mode, int seen, const uint8_t *status, const uint64_t *off, char *out,
+                           hipStream_t s);
+
 }  // namespace vcfxg

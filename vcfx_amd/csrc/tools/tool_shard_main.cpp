@@ -16,7 +16,7 @@
 //
 //   record tools (a view per rank): VCFX_allele_freq_calc, VCFX_record_filter,
 //     VCFX_genotype_query, VCFX_nonref_filter, VCFX_dosage_calculator, VCFX_hwe_tester,
-//     VCFX_missing_detector, VCFX_allele_counter (not -z)
+//     VCFX_missing_detector, VCFX_allele_counter (not -z), VCFX_sample_extractor
 //   VCFX_ld_calculator (streaming): every rank parses the file and writes the pair rows of its
 //     `--shard r/N` share (equal window-pair counts)
 // A BGZF file (.vcf.gz as bgzip writes it) is cut the same way in the coordinates of its inflated
@@ -70,6 +70,7 @@ const std::vector<ToolOpts> &tool_opts() {
         {"VCFX_hwe_tester", {"-i"}, {"--input"}, kView},
         {"VCFX_missing_detector", {"-i"}, {"--input"}, kView},
         {"VCFX_allele_counter", {"-s", "-i", "-t", "-l"}, {"--samples", "--input", "--threads", "--limit-samples"}, kView},
+        {"VCFX_sample_extractor", {"-s", "-i"}, {"--samples", "--input"}, kView},
         {"VCFX_ld_calculator", {"-i", "-r", "-w", "-t", "-n", "-d"},
          {"--input", "--region", "--window", "--threshold", "--threads", "--max-distance", "--shard"}, kRows},
     };

@@ -28,6 +28,11 @@ class IbParams(ctypes.Structure):
                 ("count_boundary_as_used", ctypes.c_int)]
 
 
+class SxParams(ctypes.Structure):
+    _fields_ = [("cols", ctypes.c_void_p), ("m", ctypes.c_uint64), ("mode", ctypes.c_int),
+                ("seen_chrom", ctypes.c_int)]
+
+
 class Criterion(ctypes.Structure):
     _fields_ = [("target", ctypes.c_int), ("op", ctypes.c_int), ("numeric", ctypes.c_int), ("value", ctypes.c_double),
                 ("key", ctypes.c_char_p), ("key_len", ctypes.c_size_t), ("str", ctypes.c_char_p),
@@ -81,6 +86,7 @@ SIGNATURES = {
     "vcfxg_allele_counter": (_I, [_VP, _U64, _U64, _VP, ctypes.POINTER(Summary)]),
     "vcfxg_inbreeding_region": (_I, [_VP, _S, _I, _VP, ctypes.POINTER(Summary)]),
     "vcfxg_inbreeding_samples": (_I, [_VP, _VP, _VP, _VP]),
+    "vcfxg_sample_extract": (_I, [_VP, _U64, _U64, _VP, ctypes.POINTER(Summary)]),
     "vcfxg_fetch_text_range": (_I, [_VP, _U64, _S, _VP]),
     "vcfxg_shard_cuts": (_I, [_VP, _S, _S, _I, _VP]),
     "vcfxg_comm_init": (_I, [_VP, _I, ctypes.POINTER(_VP)]),
@@ -333,6 +339,32 @@ class Engine:
         self._chk(self.L.vcfxg_inbreeding_samples(self.h, se.ctypes.data, oh.ctypes.data, us.ctypes.data),
                   "inbreeding_samples")
         return se, oh, us
+
+    def sample_extract(self, l0, l1, cols, mode=MODE_FILE, seen_chrom=True):
+        """VCFX_sample_extractor's rewrite of indexed lines [l0, l1) keeping the columns `cols`
+        (field numbers >= 9, ascending) (vcfxg_sample_extract).  One call takes at most
+        VCFXG_SX_BLOCK lines: the summary's n_lines says how many, and the caller goes on from
+        l0 + n_lines; text(s.text_bytes) holds their bytes, statuses their per-line status."""
+        import numpy as np
+        idx = np.ascontiguousarray(cols, np.uint32)
+        p = SxParams(idx.ctypes.data if len(idx) else None, len(idx), int(mode), int(bool(seen_chrom)))
+        s = Summary()
+        self._chk(self.L.vcfxg_sample_extract(self.h, l0, l1, ctypes.byref(p), ctypes.byref(s)), "sample_extract")
+        return s
+
+    def sample_extract_all(self, l0, l1, cols, mode=MODE_FILE, seen_chrom=True):
+        """sample_extract block by block over [l0, l1): (text, statuses, summaries)"""
+        import numpy as np
+        text, st, sums = [], [], []
+        while l0 < l1:
+            s = self.sample_extract(l0, l1, cols, mode, seen_chrom)
+            text.append(self.text(s.text_bytes))
+            b = np.zeros(max(int(s.n_lines), 1), np.uint8)
+            self._chk(self.L.vcfxg_fetch_lines(self.h, l0, s.n_lines, None, None, b.ctypes.data), "fetch_lines")
+            st.append(b[:s.n_lines])
+            sums.append(s)
+            l0 += s.n_lines
+        return b"".join(text), (np.concatenate(st) if st else np.zeros(0, np.uint8)), sums
 
     def haplotype_phaser(self, data_start, mode, threshold, n_samples):
         """VCFX_haplotype_phaser's parse + consecutive-variant LD (vcfxg_haplotype_phaser)"""
