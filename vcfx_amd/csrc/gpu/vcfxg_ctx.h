@@ -1,0 +1,262 @@
+// vcfxg_ctx.h -- the device context behind the C ABI (include/vcfx_gpu.h) and the host-side
+// helpers its translation units (vcfxg_api*.hip, vcfxg_comm.hip) share.  Private: not installed,
+// and nothing under include/ sees it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "vcfx_gpu.h"
+#include "vcfxg_kernels.h"
+#include "vcfxg_rf.h"
+
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+};
+
+struct vcfxg_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::string err;
+    // input
+    DevBuf input;
+    size_t n = 0;
+    int last_byte = -1;  // input[n-1] (host copy), -1 if empty
+    bool loaded = false;
+    bool ingesting = false;               // between vcfxg_ingest_begin and the final chunk
+    bool hints_pending = false;           // no ingested chunk has held a data line yet
+    const char *last_schedule = "";       // the schedule of the last region call (note_schedule)
+    std::vector<std::pair<size_t, hipEvent_t>> ingest_ev;  // (input bytes copied once it fires, event)
+    std::vector<hipEvent_t> ingest_ev_free;
+    // index
+    DevBuf idx_counts, idx_offs, idx_pos, line_end, d_nlines, scan_tmp;
+    size_t data_start = 0;
+    uint64_t n_lines = 0;
+    bool indexed = false;
+    // per-line results
+    DevBuf alt, tot, rowpre, status, rowlen, rowoff, text, counters, query, crit, pool;
+    std::string query_host, crit_host, pool_host;  // host sources of in-flight async copies
+    // LD
+    DevBuf ld_G, ld_lines, ld_vidx, ld_valid, ld_Gc, ld_vars, ld_plen, ld_poff, ld_prefix, ld_cid, ld_blocks, ld_cnt,
+        ld_off, ld_pairs, ld_fast, ld_gflag, ld_Gp, ld_rowoff, ld_Gv, ld_Gq, dose_meta;
+    // LD walk (vcfxg_ld_prepare_region): walker counts, valid-line counts and their scan, flags +
+    // summary; ld_gc_ready: ld_Gc holds the compact int8 rows (the walk gathers them only when
+    // some variant misses a call)
+    DevBuf ld_wcnt, ld_wval, ld_vbase, ld_small, ld_pend;
+    // vcfxg_bgzf_stage: the compressed stream's size and the bytes staged so far (into bgz_in, on
+    // copy_stream); vcfxg_bgzf_inflate: members already launched and their output bytes
+    size_t bgz_total = 0, bgz_staged = 0;
+    uint64_t bgz_handed = 0;  // members of the last BGZF ingest the lane decoder handed over
+    uint64_t bgz_launched = 0, bgz_out = 0;
+    hipStream_t copy_stream = nullptr;
+    hipEvent_t bgz_copy_ev = nullptr;  // the latest staged copy
+    // the inflate batches run round robin on their own streams (one stream would serialise each
+    // batch's tail), joined before the device input completes; two: batches are 32,768 members
+    // (hostio.cpp), and a fresh context pays ~7 ms to create a stream
+    static constexpr int kBgzStreams = 2;
+    hipStream_t bgz_stream[kBgzStreams] = {};
+    hipEvent_t bgz_ev[kBgzStreams] = {};
+    int bgz_next = 0;
+    bool ld_gc_ready = false;
+    bool ld_vq = false;  // ld_Gv / ld_Gq (valid-mask and squared-dosage FP4 planes) are current
+    int n_cu = 0;
+    DevBuf async_small;         // asynchronous AF path: line range {0, n}, failure flags, summary
+    DevBuf ld_temp, ld_quarters, ld_stage_ctr;  // LD: pairs staged by the count pass
+    uint64_t ld_temp_cap = 0;
+    // test hook: a fixed (small) staging capacity exercises the overflow -> emit-pass path
+    uint64_t ld_stage_cap_fixed = getenv("VCFXG_LD_STAGE_CAP") ? strtoull(getenv("VCFXG_LD_STAGE_CAP"), nullptr, 10) : 0;
+    DevBuf af_meta;             // AF head pass output (k_af_meta)
+    // walk AF path (vcfxg_af_walk.hip): per-walker regions, counts, scan, flags
+    DevBuf wk_le, wk_alt, wk_tot, wk_rowpre, wk_status, wk_meta, wk_count, wk_offs, wk_gt, wk_small;
+    DevBuf wk_tabs, rf_tabs;    // filter / query walk: per-line tab offsets (per walker, dense)
+    // AF walk region tail: per walker row bytes, text offsets, first line start; leftover list
+    DevBuf wk_text, wk_toff, wk_start, wk_cx, wk_bs, scratch_small, byte_cnt;
+    // AF walk: flags / counters that k_walker_scan zeroes after reading them (af_small_dirty: a
+    // call did not get that far, so the next one clears them first), and the call summary the
+    // same kernel writes straight into mapped host memory (no copy before the synchronisation)
+    DevBuf af_small;
+    bool af_small_dirty = true;
+    DevBuf wk_stage, wk_dirty;  // AF walk: each walker's rows as text (kStageCap bytes), its clean flag
+    uint64_t *sum_host = nullptr, *sum_dev = nullptr;
+    uint64_t cx_hint = ~0ull;  // leftover lines of the previous AF walk (sizes k_af_cx's grid)
+    // filter / query walk: overflow slot + 8 counters, zeroed by k_fq_done after each call
+    // (fq_small_dirty as af_small_dirty); its summary goes to sum_host[8..17]
+    DevBuf fq_small;
+    bool fq_small_dirty = true;
+    uint64_t fq_lines_hint = 0;  // lines of the previous filter / query walk (sizes k_fq_finish's grid)
+    // the bytes last uploaded to query / crit / pool and the buffer they went to: an unchanged
+    // query or criteria list is not copied again (any other writer resets the pointer)
+    std::string query_dev, crit_dev, pool_dev;
+    void *query_dev_p = nullptr, *crit_dev_p = nullptr, *pool_dev_p = nullptr;
+    // the last AF walk left its per-line results in walker regions only (ensure_dense)
+    bool dense_pending = false;
+    int64_t dense_nw = 0;
+    uint64_t dense_cap_w = 0;
+    // VCFX_hwe_tester: hom-alt counts (dense, per walker), the host-recheck list and its length
+    DevBuf hwe_aux, wk_aux, hwe_rc;
+    // VCFX_allele_counter: slots' sample indices, name offsets and bytes, per-wave sample tables
+    DevBuf ac_eff, ac_noff, ac_names, ac_scratch, ac_etab, ac_nib;
+    std::vector<uint32_t> ac_eff_host;
+    std::vector<uint64_t> ac_noff_host;
+    std::string ac_names_host;
+    std::vector<uint8_t> ac_etab_host;
+    // VCFX_haplotype_phaser: genotype rows (by line), per-line info, variant -> line, pair flags
+    DevBuf ph_G, ph_isvar, ph_info, ph_vnum, ph_vline, ph_flags, ph_r2;
+    uint64_t ph_nvar = 0;
+    uint64_t hwe_rc_n = 0;
+    // VCFX_inbreeding_calculator: one block's code rows, meta, table and walker counts; the
+    // per-sample state carried from block to block (sumExp, obsHet, usedCount, carried code)
+    DevBuf ib_codes, ib_meta, ib_tab, ib_packed, ib_cnt, ib_offs, ib_sum, ib_obs, ib_used, ib_carried, ib_small;
+    uint32_t ib_ns = 0;  // samples of the last vcfxg_inbreeding_region call (0: none yet)
+    // VCFX_sample_extractor: the kept-field bitmask; lines per call (read when the context opens;
+    // tests make many blocks, and blocks of one line, with small values)
+    DevBuf sx_mask;
+    std::vector<uint32_t> sx_mask_host;
+    uint64_t sx_block = getenv("VCFXG_SX_BLOCK")
+                            ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_SX_BLOCK"), nullptr, 10), 1), 1u << 24)
+                            : 65536;
+    // records per chain block (read when the context opens; tests cross block edges with 1, 7, 64)
+    uint64_t ib_block = getenv("VCFXG_IB_BLOCK")
+                            ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_IB_BLOCK"), nullptr, 10), 1), 1u << 24)
+                            : 65536;
+    // ulps either side of the device p-value that must print the same digits (test hook: a
+    // huge value sends every exp()-derived row to the host)
+    int64_t hwe_ulps = getenv("VCFXG_HWE_ULPS") ? atoll(getenv("VCFXG_HWE_ULPS")) : 16;
+    // (an override is clamped to [4 KiB, 8 MiB]: the AF walk packs a walker's GT-line count in
+    // 16 bits, and its line capacity 2 * chunk / hint_line + 16 stays below 2^15 for the
+    // >= 512 B records the walk takes)
+    int64_t walk_chunk = getenv("VCFXG_WALK_CHUNK")
+                             ? std::min<int64_t>(std::max<int64_t>(atol(getenv("VCFXG_WALK_CHUNK")), 4096), 8 << 20)
+                             : 128 * 1024;
+    bool walk_overflowed = false;  // the last walk run overflowed: two-sweep schedule
+    bool dose_head_failed = false;  // a dosage head walk's rows failed the check (this input)
+    bool ph_head_failed = false;    // a phaser head-walk index failed the parse's check (this input)
+    // host hints taken at load time from the first data line: its '\n' distance from the
+    // sample start (the walk's first prediction) and the mean length of the first lines
+    int64_t hint_span = 0, hint_line = 0;
+    // the first data line's FORMAT is exactly "GT" (fixed-stride records: the walk's predicted
+    // ends pay; "GT:AD:DP"-like records are scanned faster by the index sweep)
+    bool hint_gt_only = false;
+    // ... or starts with "GT:" (GT:AD:DP-like records: the GT-first walk, gt_first finding each
+    // record's end in its one sweep)
+    bool hint_gt_first = false;
+    uint64_t af_line_cap = 0;   // two-sweep AF: line capacity the last run needed
+    // region AF schedule: 0 = default (the walk schedule 7 when the first records average
+    // >= 512 B, else 3 with one host synchronisation: single-sweep index + head pass +
+    // fixed-stride sweep), 1 = one-sweep look-back kernel (k_af_fused),
+    // 2 = chunk count + chunk sweep (k_af_chunks), 4 = one sweep with byte-class segment
+    // counts (k_af_scan); the single-sweep alternatives are correct and tested but slower
+    // today, kept selectable for measurement; 7 = walk (k_af_walk: predicted
+    // record ends validated by the sweep, one HBM pass); 8 = the two-sweep schedule always
+    int af_path = getenv("VCFXG_AF_FUSED") ? atoi(getenv("VCFXG_AF_FUSED")) : 0;
+    // record_filter / genotype_query region schedule: 0 = the walk (vcfxg_fq_walk.hip) when
+    // the first records average >= 512 B, 1 = the walk always, -1 = index + per-tool kernels
+    int fq_path = getenv("VCFXG_FQ_WALK") ? atoi(getenv("VCFXG_FQ_WALK")) : 0;
+    std::vector<uint8_t> ld_gflag_host;  // per 128-variant group: all complete
+    uint64_t ld_m = 0, ld_prefix_bytes = 0, ld_np = 0;
+    int ld_kpad = 64, ld_ns = 0, ld_kp4 = 64;
+    bool ld_chrom_ids = false;
+    std::vector<uint32_t> ld_cid_host, ld_blocks_host;
+    // the last streaming call's block lists: key (j0, j1, window, M, masked kernel), group
+    // flags, list sizes (fast, masked, int8), the ld_blocks buffer they were copied to
+    uint64_t ld_plan_key[5] = {0, 0, 0, 0, 0};
+    std::vector<uint8_t> ld_plan_gf;
+    uint32_t ld_plan_n[4] = {0, 0, 0, 0};
+    // the sparse-missing LD kernel's data (ld_sp: some 256-group qualifies): CSR of each
+    // variant's missing samples and the sample-major contribution plane
+    bool ld_sp = false;
+    uint64_t ld_mp = 0;
+    DevBuf ld_moff, ld_midx, ld_mvar, ld_gt16, ld_sprec, ld_midx16;
+    // device BGZF inflate (vcfxg_ingest_bgzf): compressed bytes, member table, output offsets,
+    // per-member status, first bad member
+    DevBuf bgz_in, bgz_mem, bgz_off, bgz_stat, bgz_small, bgz_perm;
+    // the lane decoder's token buffers (and hand-over lists): one per inflate stream and one for
+    // `stream`; its side stream (the hand-overs') and events
+    DevBuf bgz_tok[kBgzStreams + 1];
+    vcfxg::InflateSide bgz_side;
+    void *ld_plan_dev = nullptr;
+    uint64_t text_bytes = 0;
+    uint64_t text_hint = 0;  // AF walk: text bytes of the previous call (the next call's capacity)
+    // profiling: an event pair per launch from a pool, harvested only when the figures are
+    // read (or the pending list is long): no event queries between the calls of a timed loop
+    bool profiling = false;
+    std::string prof_only;  // non-empty: only this kernel is timed
+    struct ProfRec {
+        const char *name;
+        hipEvent_t a, b;
+    };
+    std::vector<hipEvent_t> ev_free;
+    std::vector<ProfRec> ev_open, pending;
+    std::map<std::string, float> ms;           // last launch
+    std::map<std::string, std::pair<double, uint64_t>> acc;  // sum ms, launches
+};
+
+namespace vcfxg {
+
+constexpr size_t kPad = 256;  // zeroed bytes after the input: 16 B loads may run past n
+
+// ---- vcfxg_api.hip
+int fail(vcfxg_ctx *c, hipError_t e, const char *what);
+#define HIPCHK(ctx, x)                                          \
+    do {                                                        \
+        hipError_t e_ = (x);                                    \
+        if (e_ != hipSuccess) return vcfxg::fail(ctx, e_, #x);  \
+    } while (0)
+int ensure(vcfxg_ctx *c, DevBuf &b, size_t bytes);
+template <typename T>
+T *P(DevBuf &b) {
+    return reinterpret_cast<T *>(b.p);
+}
+// an event pair per profiled launch; prof_collect after a call harvests a long pending list
+void prof_begin(vcfxg_ctx *c, const char *name);
+void prof_end(vcfxg_ctx *c, const char *name);
+void prof_collect(vcfxg_ctx *c);
+// exclusive prefix sums of n values on the context's stream (hipcub, temporary in scan_tmp)
+int exclusive_scan(vcfxg_ctx *c, const uint32_t *in, uint64_t *out, size_t n);
+int exclusive_scan(vcfxg_ctx *c, const uint64_t *in, uint64_t *out, size_t n);
+void note_schedule(vcfxg_ctx *c, const char *what);
+bool load_hints(vcfxg_ctx *c, const char *h, size_t n);
+
+// ---- vcfxg_api_af.hip
+int ensure_dense(vcfxg_ctx *c);
+// per-line calls on the indexed context read the dense arrays
+#define DENSE(c)                          \
+    do {                                  \
+        int rd_ = vcfxg::ensure_dense(c); \
+        if (rd_) return rd_;              \
+    } while (0)
+
+// ---- vcfxg_api_walk.hip: the record walks' plan, schedule predicates and shared sequences
+int af_buffers(vcfxg_ctx *c, uint64_t L);
+int ensure_sum_host(vcfxg_ctx *c);
+// the walkers of [data_start, n): chunk C (0: the context's walk_chunk), nw walkers of cap_w line
+// slots each, cap slots in all; fits_gt16: cap_w fits the 16-bit GT-line count k_af_walk packs
+struct WalkPlan {
+    int64_t lo, hi, C, nw;
+    uint64_t cap_w, cap;
+    bool fits_gt16;
+};
+WalkPlan walk_plan(const vcfxg_ctx *c, size_t data_start, int64_t chunk = 0);
+// the input-derived half of "does this call walk": long records (of FORMAT exactly "GT" where the
+// walk's kernel needs that) and no walk overflow on this input yet
+bool walk_wanted(const vcfxg_ctx *c, bool need_gt_only);
+// VCFXG_AF_FUSED is neither 3 nor 8 (the schedules without a walk)
+bool af_knob_allows_walk(const vcfxg_ctx *c);
+int walk_buffers(vcfxg_ctx *c, const WalkPlan &p);
+int dense_buffers(vcfxg_ctx *c, uint64_t L);
+int walk_compact(vcfxg_ctx *c, int64_t nw, uint64_t cap_w, unsigned long long *counters, bool aux,
+                 const uint64_t *bpre);
+int af_walk_to_dense(vcfxg_ctx *c, const WalkPlan &p, int mode, const char *prof_name, size_t small_zero, bool aux,
+                     bool dose, bool head);
+int fq_walk_to_dense(vcfxg_ctx *c, const WalkPlan &p, int what, int strip_cr, const RfArgs &ra, const char *q_dev,
+                     int qlen, int strict, int qa, int qb, const char *walk_name, const char *rest_name);
+int fq_walk_done(vcfxg_ctx *c);
+
+}  // namespace vcfxg
