@@ -511,6 +511,11 @@ int vcfxg_count_byte(vcfxg_ctx *ctx, uint64_t from, int byte, uint64_t *count);
 /* the schedule the last region call took ("af_walk", "af_walk_gt_first", "af_two_sweep", "fq_walk",
  * "fq_two_sweep", ...): a diagnostic for tests; VCFXG_SCHEDULE_LOG=path appends one line per call */
 const char *vcfxg_last_schedule(const vcfxg_ctx *ctx);
+/* the sample sweep of the last allele-frequency walk over GT-only records: its depth in 1 KiB
+ * wave-steps (6, 8, 10 or 12; 0: no such walk yet) and, in *rolling (may be null), whether a record
+ * longer than that continues rolling; chosen from the input's sample count, or forced by
+ * VCFXG_AF_DEPTH (read when the context opens).  A diagnostic for tests */
+int vcfxg_last_af_depth(const vcfxg_ctx *ctx, int *rolling);
 
 /* device-formatted output text (without the column header line) */
 int vcfxg_fetch_text(vcfxg_ctx *ctx, char *host, size_t cap);

@@ -25,9 +25,9 @@ KERNELS = {
     "line_emit": r"vcfxg::k_idx_sweep<true>\(",
     "line_compact": r"vcfxg::k_nl_compact\(",
     "af_records": r"vcfxg::k_(line_meta|af_sweep|af_complex)\(",
-    "af_walk": r"vcfxg::k_af_walk<vcfxg::AfOp(, false)?>\(",
-    "hwe_walk": r"vcfxg::k_af_walk<vcfxg::HweOp(, false)?>\(",
-    "dose_walk": r"vcfxg::k_af_walk<vcfxg::Dose(Walk|Head)Op(, false)?>\(",
+    "af_walk": r"vcfxg::k_af_walk<vcfxg::AfOp(, false(, \d+, (true|false))?)?>\(",
+    "hwe_walk": r"vcfxg::k_af_walk<vcfxg::HweOp(, false(, \d+, false)?)?>\(",
+    "dose_walk": r"vcfxg::k_af_walk<vcfxg::Dose(Walk|Head)Op(, false(, \d+, false)?)?>\(",
     "dose_fmt": r"vcfxg::k_dose_fmt<",
     "walk_compact": r"vcfxg::k_walk_compact\(",
     "af_complex": r"vcfxg::k_af_(complex|cx)\(",

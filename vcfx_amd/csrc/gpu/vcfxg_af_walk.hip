@@ -45,6 +45,8 @@ namespace vcfxg {
 #define VCFXG_WALK_UNROLL 6
 #endif
 constexpr int kWalkUnroll = VCFXG_WALK_UNROLL;  // wave-steps (KiB) of a record in flight per sweep step
+static_assert(kWalkUnroll == kAfDepthDefault, "launch_af_walk's default depth is the batch walks' unroll");
+static_assert(kAfWaveStep == kWaveStep, "the host plan's wave-step");
 // the HWE walk's sweep: 5 wave-steps (its clean-step genotype classes need the registers of the
 // sixth under the 96-VGPR bound; at 6 the record loop spilled)
 #ifndef VCFXG_HWE_UNROLL
@@ -127,18 +129,30 @@ struct WalkRed<DoseHeadOp> : WalkRed<DoseWalkOp> {
 // record whose '\n' is past the window is swept by gt_first from its sample start, which finds
 // the record's end in the same pass (and issues the next window as soon as it does); a separate
 // instantiation, so the GT-only walk keeps its registers
-template <class Op, bool kGF = false>
+//
+// kDepth / kRoll (the AfOp GT-only walk alone; every other walk keeps kWalkUnroll and its batches):
+// the wave-steps af_fixed keeps in flight, and whether a record longer than that continues
+// rolling, with non-temporal loads (af_fixed's kRoll path).  A record that fits kDepth wave-steps
+// is fetched in ONE round trip to HBM; the 6-step batches pay two in sequence on a 10 KB record.
+// Measured: the loads' policy is 7-10 % of the walk, the depth 1-2 % on top of it.
+// launch_af_walk dispatches over the compiled (kDepth, kRoll); the plan chooses (walk_plan)
+#ifndef VCFXG_AF_MINW
+#define VCFXG_AF_MINW 5
+#endif
+// waves per SIMD of an instantiation: the GT-first walk at <= 128 VGPRs (4 waves; it needs 129
+// unconstrained, which rounds to 136 and 3 waves); the others at <= 96 (5 waves: the HWE walk
+// took 100 without the bound, 4 waves; no spills at 96), but the AF walk's deeper sweeps, whose
+// 4 VGPRs a wave-step do not fit 96 without scratch: 4 waves from depth 10
+#ifndef VCFXG_AF_DEEP_MINW
+#define VCFXG_AF_DEEP_MINW 4
+#endif
+constexpr int af_walk_waves(bool gf, int depth) { return gf ? 4 : depth >= 10 ? VCFXG_AF_DEEP_MINW : VCFXG_AF_MINW; }
+template <class Op, bool kGF = false, int kDepth = kWalkUnroll, bool kRoll = false>
 __global__ __launch_bounds__(kWalkThreads)
 #ifdef VCFXG_WALK_MAXW
 __attribute__((amdgpu_waves_per_eu(1, VCFXG_WALK_MAXW)))
 #else
-// the GT-first walk at <= 128 VGPRs (4 waves per SIMD; it needs 129 unconstrained, which
-// rounds to 136 and 3 waves); the others at <= 96 (5 waves: the HWE walk took 100 without
-// the bound, 4 waves; no spills at 96)
-#ifndef VCFXG_AF_MINW
-#define VCFXG_AF_MINW 5
-#endif
-__attribute__((amdgpu_waves_per_eu(kGF ? 4 : VCFXG_AF_MINW)))
+__attribute__((amdgpu_waves_per_eu(af_walk_waves(kGF, kDepth))))
 #endif
 void k_af_walk(const char *__restrict__ buf, int64_t lo, int64_t hi, int64_t chunk, int64_t n_walkers, int mode,
                int64_t span0, uint64_t cap_w, uint64_t *__restrict__ le_o, int32_t *__restrict__ alt_o,
@@ -146,6 +160,10 @@ void k_af_walk(const char *__restrict__ buf, int64_t lo, int64_t hi, int64_t chu
                uint8_t *__restrict__ status_o, LineMeta *__restrict__ meta_o, uint64_t *__restrict__ wcount,
                uint32_t *__restrict__ wgt, unsigned *overflow, WalkTail tail) {
     typedef WalkRed<Op> R;
+    static_assert((kDepth == kWalkUnroll && !kRoll) || (std::is_same<Op, AfOp>::value && !kGF),
+                  "k_af_walk: a depth of its own for the AF GT-only walk alone");
+    static_assert((kDepth == kWalkUnroll && !kRoll) || !(VCFXG_AF_XREC || VCFXG_AF_EARLY),
+                  "k_af_walk: the carried / early loads are batch-path experiments at kWalkUnroll");
     __shared__ uint4 win[kWalkWaves][2][kWave];  // two window slots per wave (double buffer)
     // (AfOp) each walker's rows composed in LDS and copied to its global stage once, at the end:
     // stored per record, their completion held up the next record's window wait (r05 ablation:
@@ -378,7 +396,7 @@ void k_af_walk(const char *__restrict__ buf, int64_t lo, int64_t hi, int64_t chu
                     ok = af_fixed<kWalkUnroll>(buf, S, ae, op, sep, pre, mine ? ev : nullptr, mine ? eA : -1);
                     eA = -1;
                 } else if constexpr (std::is_same<Op, AfOp>::value)
-                    ok = af_fixed < kGF ? kGfUnroll : kWalkUnroll > (buf, S, ae, op, sep, pre);
+                    ok = af_fixed < kGF ? kGfUnroll : kDepth, kRoll > (buf, S, ae, op, sep, pre);
                 else if constexpr (std::is_same<Op, DoseHeadOp>::value) {
                     if (skip) {  // samples (ae - S + 1) / 4, none "NA" (checked by k_dose_fmt)
                         ok = (sep == '/' || sep == '|') && ae - S >= 3 && ((ae - S + 1) & 3) == 0;
@@ -572,10 +590,14 @@ hipError_t launch_af_walk(const char *buf, int64_t lo, int64_t hi, int64_t chunk
                           uint64_t cap_w, uint64_t *le_b, int32_t *alt_b, int32_t *tot_b, uint32_t *rowpre_b,
                           uint8_t *status_b, void *meta_b, uint64_t *wcount, uint32_t *wgt, unsigned *overflow,
                           hipStream_t s, int32_t *hwe_aux_b, const WalkTail *tail, bool dose, bool gt_first_walk,
-                          bool dose_head) {
+                          bool dose_head, int depth, bool roll) {
     const WalkTail t = tail ? *tail : WalkTail{};
     const int64_t nw = af_walkers(lo, hi, chunk);
     if (!nw) return hipErrorInvalidValue;
+    // the compiled sweeps: the batches of kWalkUnroll wave-steps for every walk; for the AF GT-only
+    // walk also the rolling sweeps of af_depth_compiled
+    const bool af_gt_only = !gt_first_walk && !dose && !hwe_aux_b;
+    if (roll ? !(af_gt_only && af_depth_compiled(depth)) : depth != kWalkUnroll) return hipErrorInvalidValue;
     const unsigned grid = (unsigned)((nw + kWalkWaves - 1) / kWalkWaves);
     if (gt_first_walk)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_af_walk<AfOp, true>), dim3(grid), dim3(kWalkThreads), 0, s, buf, lo, hi,
@@ -593,10 +615,18 @@ hipError_t launch_af_walk(const char *buf, int64_t lo, int64_t hi, int64_t chunk
         hipLaunchKernelGGL(k_af_walk<HweOp>, dim3(grid), dim3(kWalkThreads), 0, s, buf, lo, hi, chunk, nw, mode, span0,
                            cap_w, le_b, alt_b, tot_b, hwe_aux_b, rowpre_b, status_b, static_cast<LineMeta *>(meta_b),
                            wcount, wgt, overflow, t);
-    else
-        hipLaunchKernelGGL(k_af_walk<AfOp>, dim3(grid), dim3(kWalkThreads), 0, s, buf, lo, hi, chunk, nw, mode, span0,
-                           cap_w, le_b, alt_b, tot_b, nullptr, rowpre_b, status_b, static_cast<LineMeta *>(meta_b),
-                           wcount, wgt, overflow, t);
+    else {
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kWalkThreads), 0, s, buf, lo, hi, chunk, nw, mode, span0, cap_w,
+                               le_b, alt_b, tot_b, nullptr, rowpre_b, status_b, static_cast<LineMeta *>(meta_b), wcount,
+                               wgt, overflow, t);
+        };
+        if (!roll) go(k_af_walk<AfOp>);  // (depth kWalkUnroll: checked above)
+        else if (depth == 6) go(k_af_walk<AfOp, false, 6, true>);
+        else if (depth == 8) go(k_af_walk<AfOp, false, 8, true>);
+        else if (depth == 10) go(k_af_walk<AfOp, false, 10, true>);
+        else go(k_af_walk<AfOp, false, 12, true>);
+    }
     return hipGetLastError();
 }
 

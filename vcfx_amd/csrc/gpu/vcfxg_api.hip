@@ -595,6 +595,10 @@ int vcfxg_shard_cuts(const char *data, size_t n, size_t lo, int world, uint64_t 
 }
 
 const char *vcfxg_last_schedule(const vcfxg_ctx *c) { return c ? c->last_schedule : ""; }
+int vcfxg_last_af_depth(const vcfxg_ctx *c, int *rolling) {
+    if (rolling) *rolling = c && c->last_af_roll ? 1 : 0;
+    return c ? c->last_af_depth : 0;
+}
 uint64_t vcfxg_bgzf_handed_over(const vcfxg_ctx *c) { return c ? c->bgz_handed : 0; }
 
 int vcfxg_fetch_text_range(vcfxg_ctx *c, uint64_t offset, size_t n, void *host) {

@@ -205,11 +205,16 @@ static int af_region_walk(vcfxg_ctx *c, size_t data_start, int mode, vcfxg_summa
     tail.stage = P<char>(c->wk_stage);
     tail.stage_cap = kStageCap;
     tail.wdirty = P<uint8_t>(c->wk_dirty);
+    // (the GT-first walk has one sweep of its own)
+    const int depth = gf ? vcfxg::kAfDepthDefault : pl.af_depth;
+    const bool roll = !gf && pl.af_roll;
+    if (!gf) c->last_af_depth = depth, c->last_af_roll = roll;
     prof_begin(c, "af_walk");
     HIPCHK(c, vcfxg::launch_af_walk(buf, lo, hi, C, mode, c->hint_span, cap_w, P<uint64_t>(c->wk_le),
                                     P<int32_t>(c->wk_alt), P<int32_t>(c->wk_tot), P<uint32_t>(c->wk_rowpre),
                                     P<uint8_t>(c->wk_status), c->wk_meta.p, P<uint64_t>(c->wk_count),
-                                    P<uint32_t>(c->wk_gt), ovf, c->stream, nullptr, &tail, false, gf));
+                                    P<uint32_t>(c->wk_gt), ovf, c->stream, nullptr, &tail, false, gf, false, depth,
+                                    roll));
     prof_end(c, "af_walk");
     prof_begin(c, "af_complex");
     // the grid: a wave per leftover line of the previous call (usually none; 16 blocks at least)

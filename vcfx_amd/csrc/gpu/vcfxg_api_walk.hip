@@ -4,6 +4,14 @@
 // with its reducers, the filter / query walk).  Each entry point keeps its own knobs.
 #include "vcfxg_ctx.h"
 
+// VCFXG_AF_DEPTH_LIVE=1 (A/B builds only): VCFXG_AF_DEPTH is read at every call instead of when
+// the context opens, and 1 selects the batches of kAfDepthDefault whatever the input -- so ONE
+// context, with one placement of the input in HBM, times every sweep (two contexts running the
+// same kernel on the same bytes differed by 3 % here: as much as the sweeps differ)
+#ifndef VCFXG_AF_DEPTH_LIVE
+#define VCFXG_AF_DEPTH_LIVE 0
+#endif
+
 namespace vcfxg {
 
 WalkPlan walk_plan(const vcfxg_ctx *c, size_t data_start, int64_t chunk) {
@@ -21,7 +29,40 @@ WalkPlan walk_plan(const vcfxg_ctx *c, size_t data_start, int64_t chunk) {
     // slots.  (The HWE walk launches k_af_walk too but never reads the packed count -- it zeroes
     // `counters` after the compaction -- and the fq, md and ib walks pack none: no check there.)
     p.fits_gt16 = p.cap_w <= 0xFFFF;
+    int knob = c->af_depth_knob;
+#if VCFXG_AF_DEPTH_LIVE
+    knob = getenv("VCFXG_AF_DEPTH") ? atoi(getenv("VCFXG_AF_DEPTH")) : 0;
+#endif
+    af_sweep_plan(c->hint_span, knob, p.af_depth, p.af_roll);
     return p;
+}
+
+// The AF GT-only walk's sweep for records of `span` sample bytes (the hinted 4 * samples - 1; up
+// to 15 more before the sample start in the sweep's first 16 B block): kMeasuredDepth[wave-steps
+// of the record], the depth whose rolling, non-temporal sweep an A/B on that record size showed
+// faster than the batches of kAfDepthDefault (0: none, those batches -- today's kernel bit for
+// bit).  Measured so far: 10 wave-steps, the 2,504-sample shard, where depth 10 (the
+// whole record in one batch, 4 waves per SIMD) ran 8-10 % under the default in one context, 1-2 %
+// under the rolling depths 6 and 12 and 3 % under 8.  Records of other sizes, and those longer
+// than kAfDepthMax steps, keep the default until they are measured.
+static constexpr int kMeasuredDepth[kAfDepthMax + 1] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 10, 0, 0};
+void af_sweep_plan(int64_t span, int knob, int &depth, bool &roll) {
+    depth = kAfDepthDefault;
+    roll = false;
+#if VCFXG_AF_DEPTH_LIVE
+    if (knob == 1) return;
+#endif
+    if (af_depth_compiled(knob)) {
+        depth = knob;
+        roll = true;
+        return;
+    }
+    if (span <= 0) return;
+    const int64_t steps = (span + 15 + kAfWaveStep - 1) / kAfWaveStep;
+    if (steps <= kAfDepthMax && af_depth_compiled(kMeasuredDepth[steps])) {
+        depth = kMeasuredDepth[steps];
+        roll = true;
+    }
 }
 
 bool walk_wanted(const vcfxg_ctx *c, bool need_gt_only) {
@@ -105,7 +146,7 @@ int af_walk_to_dense(vcfxg_ctx *c, const WalkPlan &p, int mode, const char *prof
                              P<int32_t>(c->wk_alt), P<int32_t>(c->wk_tot), P<uint32_t>(c->wk_rowpre),
                              P<uint8_t>(c->wk_status), c->wk_meta.p, P<uint64_t>(c->wk_count), P<uint32_t>(c->wk_gt),
                              P<unsigned>(c->wk_small), c->stream, aux ? P<int32_t>(c->wk_aux) : nullptr, nullptr, dose,
-                             false, head));
+                             false, head, kAfDepthDefault, false));  // (the HWE / dosage walks: their own sweeps)
     prof_end(c, prof_name);
     prof_begin(c, "walk_compact");
     r = exclusive_scan(c, P<uint64_t>(c->wk_count), P<uint64_t>(c->wk_offs), (size_t)p.nw + 1);

@@ -156,6 +156,11 @@ struct vcfxg_ctx {
     // today, kept selectable for measurement; 7 = walk (k_af_walk: predicted
     // record ends validated by the sweep, one HBM pass); 8 = the two-sweep schedule always
     int af_path = getenv("VCFXG_AF_FUSED") ? atoi(getenv("VCFXG_AF_FUSED")) : 0;
+    // the AF GT-only walk's sweep depth in wave-steps: 0 = the plan's choice (walk_plan), 6 / 8 /
+    // 10 / 12 = that depth, rolling past it (tests, A/B); any other value is the plan's choice
+    int af_depth_knob = getenv("VCFXG_AF_DEPTH") ? atoi(getenv("VCFXG_AF_DEPTH")) : 0;
+    int last_af_depth = 0;        // the depth / rolling of the last AF GT-only walk launched
+    bool last_af_roll = false;    // (vcfxg_last_af_depth; 0: none yet)
     // record_filter / genotype_query region schedule: 0 = the walk (vcfxg_fq_walk.hip) when
     // the first records average >= 512 B, 1 = the walk always, -1 = index + per-tool kernels
     int fq_path = getenv("VCFXG_FQ_WALK") ? atoi(getenv("VCFXG_FQ_WALK")) : 0;
@@ -238,12 +243,18 @@ int af_buffers(vcfxg_ctx *c, uint64_t L);
 int ensure_sum_host(vcfxg_ctx *c);
 // the walkers of [data_start, n): chunk C (0: the context's walk_chunk), nw walkers of cap_w line
 // slots each, cap slots in all; fits_gt16: cap_w fits the 16-bit GT-line count k_af_walk packs
+// af_depth / af_roll: the AF GT-only walk's sweep (launch_af_walk depth / roll), from the hinted
+// sample span: a rolling non-temporal sweep of the depth that the A/B of that record size showed
+// faster, else the batches of kAfDepthDefault; VCFXG_AF_DEPTH forces a compiled depth
 struct WalkPlan {
     int64_t lo, hi, C, nw;
     uint64_t cap_w, cap;
     bool fits_gt16;
+    int af_depth;
+    bool af_roll;
 };
 WalkPlan walk_plan(const vcfxg_ctx *c, size_t data_start, int64_t chunk = 0);
+void af_sweep_plan(int64_t span, int knob, int &depth, bool &roll);
 // the input-derived half of "does this call walk": long records (of FORMAT exactly "GT" where the
 // walk's kernel needs that) and no walk overflow on this input yet
 bool walk_wanted(const vcfxg_ctx *c, bool need_gt_only);

@@ -59,6 +59,12 @@ __device__ __forceinline__ uint4 bload16(__amdgpu_buffer_rsrc_t r, int off) {
     const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
     return uint4{v[0], v[1], v[2], v[3]};
 }
+// the same load non-temporal (`buffer_load_dwordx4 ... nt`): bytes read once and never again by
+// anyone, so they should displace nothing in the caches on their way through
+__device__ __forceinline__ uint4 bload16_nt(__amdgpu_buffer_rsrc_t r, int off) {
+    const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 2);  // (aux bit 1: nt on gfx94x / gfx950)
+    return uint4{v[0], v[1], v[2], v[3]};
+}
 __device__ __forceinline__ uint32_t bload4(__amdgpu_buffer_rsrc_t r, int off) {
     return __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0);
 }

@@ -15,13 +15,6 @@
 
 #include "vcfxg_device.h"
 
-// af_fixed's loads: a batch of kUnroll wave-steps per sweep step (default), or rolling
-// (VCFXG_AF_ROLL=1: a step's loads re-issued as soon as it is consumed).  r04 A/B on one box,
-// 2 alternations each (af_walk ms): batch 0.896-0.904, rolling 0.969-0.970, rolling at 5 steps
-// 0.916-0.919 -- the rolling variant's extra VGPRs cost occupancy
-#ifndef VCFXG_AF_ROLL
-#define VCFXG_AF_ROLL 0
-#endif
 // gt_first_af's loads through a per-batch buffer resource (1) or clamped global addresses (0)
 #ifndef VCFXG_GF_BUF
 #define VCFXG_GF_BUF 1
@@ -582,7 +575,16 @@ __device__ bool gt_first_af(const char *__restrict__ buf, int64_t S, int64_t hi,
 // ---------------------------------------------------------------------------------------
 // (first / vb: the walk's early loads -- the first kUnroll wave-steps from vb (16-aligned, <= S),
 // issued before the record's head was analysed; vb < 0: none)
-template <int kUnroll, class Pre>
+// kRoll: a record longer than one batch (kUnroll wave-steps) continues rolling -- step u of the
+// next batch is issued into step u's registers as soon as they are read, so the wave never drains
+// between a record's batches; a record of one batch takes the same path either way (no re-issue:
+// the batch after it starts past the record).  Without kRoll each batch is issued whole after the
+// one before it was counted (r04 A/B on one box at kUnroll = 6, af_walk ms: batch 0.896-0.904,
+// rolling 0.969-0.970, rolling at 5 steps 0.916-0.919: the rolling loop's extra VGPRs cost
+// occupancy there).  The rolling sweep's loads are non-temporal (bload16_nt): the sample bytes
+// are read once, and kept out of the caches' replacement the same sweeps ran 7-10 % faster in one
+// context (the gain of this path; the depth adds 1-2 % on top of it)
+template <int kUnroll, bool kRoll = false, class Pre>
 __device__ bool af_fixed(const char *__restrict__ buf, int64_t S, int64_t E, AfOp &op, uint32_t sep_hint, Pre pre,
                          const uint4 *first = nullptr, int64_t vb = -1) {
     S = uniform64(S);
@@ -607,25 +609,20 @@ __device__ bool af_fixed(const char *__restrict__ buf, int64_t S, int64_t E, AfO
     const int lo16 = lane() * kBlockBytes;
     uint32_t alt = 0, dots = 0, err = 0, alt8 = 0;
     static_assert(4 * kUnroll <= 255, "af_fixed: bytewise allele sums");
-#if VCFXG_AF_ROLL
-    // rolling loads: as soon as a wave-step's registers are read, the same step of the next batch
-    // is issued into them, so kUnroll steps stay in flight across batches (no bubble between a
-    // record's batches) at no register cost
     uint4 v[kUnroll];
+    if constexpr (kRoll) {  // (the walk's early loads are a batch-path experiment: not taken here)
 #pragma unroll
-    for (int u = 0; u < kUnroll; u++) v[u] = bload16(rs, u * kWaveStep + lo16);
-    pre();
-#endif
+        for (int u = 0; u < kUnroll; u++) v[u] = bload16_nt(rs, u * kWaveStep + lo16);
+        pre();
+    }
     for (int w0 = 0; w0 < Er; w0 += kUnroll * kWaveStep) {
-#if !VCFXG_AF_ROLL
-        uint4 v[kUnroll];
+        if constexpr (!kRoll) {
 #pragma unroll
-        for (int u = 0; u < kUnroll; u++) v[u] = first && w0 == 0 ? first[u] : bload16(rs, w0 + u * kWaveStep + lo16);
-        if (w0 == 0) pre();
-#endif
-#if VCFXG_AF_ROLL
+            for (int u = 0; u < kUnroll; u++)
+                v[u] = first && w0 == 0 ? first[u] : bload16(rs, w0 + u * kWaveStep + lo16);
+            if (w0 == 0) pre();
+        }
         const int wn = w0 + kUnroll * kWaveStep;  // the next batch (wave-uniform)
-#endif
         // the step's dwords, bytes outside [S, E) replaced by the expected ones (edge steps only)
         auto dwords = [&](int u, const uint4 &x, uint32_t(&d)[4]) {
             d[0] = x.x, d[1] = x.y, d[2] = x.z, d[3] = x.w;
@@ -644,9 +641,8 @@ __device__ bool af_fixed(const char *__restrict__ buf, int64_t S, int64_t E, AfO
         for (int u = 0; u < kUnroll; u++) {
             uint32_t d[4];
             dwords(u, v[u], d);
-#if VCFXG_AF_ROLL
-            if (wn < Er) v[u] = bload16(rs, wn + u * kWaveStep + lo16);
-#endif
+            if constexpr (kRoll)  // (wave-uniform: only the steps that hold bytes of the record)
+                if (wn + u * kWaveStep < Er) v[u] = bload16_nt(rs, wn + u * kWaveStep + lo16);
             // a clean step (berr = 0) has e = bit 0 of the '1' allele bytes alone: its count is
             // the byte sum of the e's, added bytewise (at most 4 kUnroll <= 255 per byte) and
             // folded into alt once per batch (v_sad_u8) -- two adds a step, not four popcounts

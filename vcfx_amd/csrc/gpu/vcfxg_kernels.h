@@ -103,11 +103,19 @@ struct WalkTail {
     uint32_t stage_cap = 0;
     uint8_t *wdirty = nullptr;
 };
+// depth / roll: the sample sweep's wave-steps (KiB of a record) in flight, and whether a record
+// longer than that continues rolling (vcfxg_gt.h af_fixed).  Every walk is compiled for the
+// batches of kAfDepthDefault; the AF GT-only walk also for the rolling sweeps of
+// af_depth_compiled.  Anything else: hipErrorInvalidValue
+constexpr int kAfDepthDefault = 6, kAfDepthMax = 12;
+constexpr int kAfWaveStep = 1024;  // bytes of a wave-step (vcfxg_device.h kWaveStep, for the host's plan)
+constexpr bool af_depth_compiled(int d) { return d == 6 || d == 8 || d == 10 || d == 12; }
 hipError_t launch_af_walk(const char *buf, int64_t lo, int64_t hi, int64_t chunk, int mode, int64_t span0,
                           uint64_t cap_w, uint64_t *le_b, int32_t *alt_b, int32_t *tot_b, uint32_t *rowpre_b,
                           uint8_t *status_b, void *meta_b, uint64_t *wcount, uint32_t *wgt, unsigned *overflow,
                           hipStream_t s, int32_t *hwe_aux_b = nullptr, const WalkTail *tail = nullptr,
-                          bool dose = false, bool gt_first_walk = false, bool dose_head = false);
+                          bool dose = false, bool gt_first_walk = false, bool dose_head = false,
+                          int depth = kAfDepthDefault, bool roll = false);
 // AF region tail without the dense per-line arrays (vcfxg_kernels.hip):
 //   launch_af_cx       the walk's leftover slots: af_line / the general sweep, new rows' bytes
 //                      added to their walker's total (counters as k_af_complex)

@@ -95,6 +95,7 @@ SIGNATURES = {
     "vcfxg_comm_destroy": (None, [_VP]),
     "vcfxg_comm_rccl_stats": (_I, [_VP, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "vcfxg_last_schedule": (_P, [_VP]),
+    "vcfxg_last_af_depth": (_I, [_VP, ctypes.POINTER(_I)]),
     "vcfxg_bgzf_handed_over": (_U64, [_VP]),
     "vcfxg_count_byte": (_I, [_VP, _U64, _I, ctypes.POINTER(_U64)]),
     "vcfxg_haplotype_phaser": (_I, [_VP, _S, _I, ctypes.c_double, ctypes.c_uint32, ctypes.POINTER(Summary)]),
@@ -258,6 +259,12 @@ class Engine:
         s = Summary()
         self._chk(self.L.vcfxg_allele_freq_region(self.h, data_start, mode, ctypes.byref(s)), "allele_freq_region")
         return s
+
+    def last_af_depth(self):
+        """(depth in wave-steps, rolling) of the last AF walk over GT-only records; (0, False): none yet."""
+        r = ctypes.c_int()
+        d = self.L.vcfxg_last_af_depth(self.h, ctypes.byref(r))
+        return d, bool(r.value)
 
     def genotype_query(self, query, strict=False, strip_cr=False):
         q = query.encode() if isinstance(query, str) else query
