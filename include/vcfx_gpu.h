@@ -406,6 +406,52 @@ typedef struct {
 int vcfxg_sample_extract(vcfxg_ctx *ctx, uint64_t first_line, uint64_t last_line, const vcfxg_sx_params *params,
                          vcfxg_summary *out);
 
+/* ---- VCFX_cross_sample_concordance (a set question per record: its distinct genotypes) --------
+ * Over the lines from data_start (the byte after the first '#CHROM' line): per record the keys of
+ * parseGenotypeToId (VCFX_cross_sample_concordance.cpp:130-167: the first ':' sub-field, digits,
+ * one '/' or '|', digits, an empty run reading as 0, anything after ignored; invalid when it
+ * starts with '.', lacks the separator, or an allele is above numAlt of countAltAlleles :170-178
+ * or above 127; the key is the sorted pair) over the selected sample columns; N = the valid keys
+ * (each counted as often as its column is selected), U = the distinct ones; the row
+ * "CHROM\tPOS\tID\tREF\tALT\t<N>\t<U>\tCONCORDANT|DISCORDANT\n", or "...\t0\t0\tNO_GENOTYPES\n"
+ * when N = 0.  mode VCFXG_MODE_FILE = calculateConcordanceMmapParallel + processVariantLine
+ * (:229-319, :445-581): '\r' stripped, empty and '#' lines dropped, a row for a line of >= 5
+ * fields with a non-empty CHROM, selected columns past the line skipped; with threads = T > 0 the
+ * rows stand in the reference's order for T workers (clamped to the data lines; worker t takes
+ * data lines t, t + T, ... and the workers' rows follow one another), written there directly.
+ * VCFXG_MODE_STDIN = calculateConcordance (:649-716): no strip, a row for a line of at least
+ * max(8, 9 + n_samples) fields; pass threads = 0 (record order).
+ * Text via vcfxg_fetch_text (without the column header); per line via vcfxg_fetch_lines: alt = N,
+ * total = U, status 0 no row / VCFXG_CC_CONCORDANT / VCFXG_CC_DISCORDANT / VCFXG_CC_NO_GENOTYPES.
+ * rows = output rows, data_lines = the collected data lines (non-empty, not '#'), n_lines,
+ * text_bytes.  For long records whose every header column is selected once (mult NULL or all
+ * ones) the device counts the fixed-stride records on the record walk (one HBM pass) and parses
+ * only the lines it leaves with the per-line kernel; otherwise that kernel takes every line after
+ * the line index.  general_records = the data lines the per-line kernel parsed.  The schedule
+ * follows VCFXG_AF_FUSED (7 the walk, 3 / 8 the line index) and VCFXG_WALK_CHUNK as the other
+ * region calls do; the context is indexed afterwards.
+ * Two things are undefined in the reference and not reproduced: a digit run that overflows int,
+ * and a file-mode row longer than 4,095 bytes. */
+#define VCFXG_CC_CONCORDANT 1
+#define VCFXG_CC_DISCORDANT 2
+#define VCFXG_CC_NO_GENOTYPES 3
+typedef struct {
+    uint32_t n_samples;   /* the header's sample count (stdin mode's field rule; the columns selected when mult is NULL) */
+    const uint32_t *mult; /* per sample column (field 9 + i) how often it is selected: 0 = not, 2 and
+                             more = repeated '#CHROM' lines; NULL = each of the first n_samples once */
+    uint64_t n_mult;      /* entries of mult */
+    uint64_t threads;     /* T of the file mode's row order; 0 = record order */
+} vcfxg_cc_params;
+int vcfxg_concordance_region(vcfxg_ctx *ctx, size_t data_start, int mode, const vcfxg_cc_params *params,
+                             vcfxg_summary *out);
+/* the last vcfxg_concordance_region call's totals: concordant, discordant and no-genotype rows,
+ * data lines */
+int vcfxg_concordance_totals(const vcfxg_ctx *ctx, uint64_t totals[4]);
+/* the start offsets, ascending, of the lines from data_start that begin with "#CHROM" (the file
+ * mode reads every one of them before any record): *n = their number; when it exceeds cap the
+ * caller repeats the call with room for all.  The context is indexed from data_start afterwards. */
+int vcfxg_chrom_lines(vcfxg_ctx *ctx, size_t data_start, uint64_t *starts, uint64_t cap, uint64_t *n);
+
 /* ---- VCFX_haplotype_phaser (LD reuse in block phasing) ------------------
  * Over the lines from data_start (the byte after the '#CHROM' line): per line status 1 variant,
  * 4 '#' line, 3 "<10 fields", 7 invalid POS, 8 no GT in FORMAT, 0 empty (mode VCFXG_MODE_FILE:

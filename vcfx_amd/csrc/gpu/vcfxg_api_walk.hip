@@ -132,7 +132,7 @@ int walk_compact(vcfxg_ctx *c, int64_t nw, uint64_t cap_w, unsigned long long *c
 // GT-line counts.  The first small_zero bytes of wk_small are zeroed; its first word is the
 // walk's overflow flag.  The walk is profiled as prof_name, the rest as "walk_compact".
 int af_walk_to_dense(vcfxg_ctx *c, const WalkPlan &p, int mode, const char *prof_name, size_t small_zero, bool aux,
-                     bool dose, bool head) {
+                     bool dose, bool head, bool cc) {
     int r = walk_buffers(c, p);
     if (!r && aux) r = ensure(c, c->wk_aux, 4 * p.cap);
     if (!r) r = ensure(c, c->wk_small, 128);
@@ -142,7 +142,13 @@ int af_walk_to_dense(vcfxg_ctx *c, const WalkPlan &p, int mode, const char *prof
     HIPCHK(c, hipMemsetAsync(c->wk_small.p, 0, small_zero, c->stream));
     HIPCHK(c, hipMemsetAsync(P<uint64_t>(c->wk_count) + p.nw, 0, 8, c->stream));
     prof_begin(c, prof_name);
-    HIPCHK(c, launch_af_walk(P<char>(c->input), p.lo, p.hi, p.C, mode, c->hint_span, p.cap_w, P<uint64_t>(c->wk_le),
+    if (cc)
+        HIPCHK(c, launch_cc_walk(P<char>(c->input), p.lo, p.hi, p.C, mode, c->hint_span, p.cap_w, P<uint64_t>(c->wk_le),
+                                 P<int32_t>(c->wk_alt), P<int32_t>(c->wk_tot), P<uint32_t>(c->wk_rowpre),
+                                 P<uint8_t>(c->wk_status), c->wk_meta.p, P<uint64_t>(c->wk_count), P<uint32_t>(c->wk_gt),
+                                 P<unsigned>(c->wk_small), c->stream));
+    else
+        HIPCHK(c, launch_af_walk(P<char>(c->input), p.lo, p.hi, p.C, mode, c->hint_span, p.cap_w, P<uint64_t>(c->wk_le),
                              P<int32_t>(c->wk_alt), P<int32_t>(c->wk_tot), P<uint32_t>(c->wk_rowpre),
                              P<uint8_t>(c->wk_status), c->wk_meta.p, P<uint64_t>(c->wk_count), P<uint32_t>(c->wk_gt),
                              P<unsigned>(c->wk_small), c->stream, aux ? P<int32_t>(c->wk_aux) : nullptr, nullptr, dose,

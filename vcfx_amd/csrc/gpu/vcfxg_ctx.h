@@ -122,6 +122,10 @@ struct vcfxg_ctx {
     uint64_t sx_block = getenv("VCFXG_SX_BLOCK")
                             ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_SX_BLOCK"), nullptr, 10), 1), 1u << 24)
                             : 65536;
+    // VCFX_cross_sample_concordance: column multiplicities, data-line flags and their scan, the
+    // "#CHROM" line list, the summary words; the last call's totals
+    DevBuf cc_mult, cc_isdata, cc_ord, cc_chrom, cc_small;
+    uint64_t cc_totals[4] = {0, 0, 0, 0};
     // records per chain block (read when the context opens; tests cross block edges with 1, 7, 64)
     uint64_t ib_block = getenv("VCFXG_IB_BLOCK")
                             ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_IB_BLOCK"), nullptr, 10), 1), 1u << 24)
@@ -265,7 +269,7 @@ int dense_buffers(vcfxg_ctx *c, uint64_t L);
 int walk_compact(vcfxg_ctx *c, int64_t nw, uint64_t cap_w, unsigned long long *counters, bool aux,
                  const uint64_t *bpre);
 int af_walk_to_dense(vcfxg_ctx *c, const WalkPlan &p, int mode, const char *prof_name, size_t small_zero, bool aux,
-                     bool dose, bool head);
+                     bool dose, bool head, bool cc = false);
 int fq_walk_to_dense(vcfxg_ctx *c, const WalkPlan &p, int what, int strip_cr, const RfArgs &ra, const char *q_dev,
                      int qlen, int strict, int qa, int qb, const char *walk_name, const char *rest_name);
 int fq_walk_done(vcfxg_ctx *c);

@@ -1064,4 +1064,51 @@ struct HweOp {
     }
 };
 
+// ---------------------------------------------------------------------------------------
+// VCFX_cross_sample_concordance's reducer on the fixed-stride layout: the record's valid
+// genotype keys and how many different ones there are.  parseGenotypeToId
+// (VCFX_cross_sample_concordance.cpp:130-167) on "a s b": valid iff both alleles are digits
+// (a '.' in either slot is not) and neither is above max_allele (numAlt of the record head);
+// the key is the sorted pair, one of 55: bit hi (hi + 1) / 2 + lo of the lane's key set.
+// finish() sums the valid samples and ORs the key sets over the wave.
+// ---------------------------------------------------------------------------------------
+struct CcOp {
+    uint32_t max_allele = 0;
+    uint32_t N = 0, U = 0;  // valid samples, distinct keys (after finish())
+    uint32_t klo = 0, khi = 0, nv = 0;
+    __device__ void begin(uint32_t, uint32_t) {}
+    __device__ bool done() const { return false; }
+    __device__ void dword(const DwordView &v) {
+        const uint32_t a = v.f & 0xFFu, b = v.f >> 16;
+        const uint32_t hi = a > b ? a : b, lo = a > b ? b : a;
+        const bool ok = v.dig == 0x01000100u && hi <= max_allele;
+        const uint32_t idx = (hi * (hi + 1u) / 2u + lo) & 63u, bit = 1u << (idx & 31u);
+        klo |= ok && idx < 32u ? bit : 0u;
+        khi |= ok && idx >= 32u ? bit : 0u;
+        nv += ok;
+    }
+    // four samples of alleles 0 / 1: the keys (0,0), (0,1), (1,1) are bits 0, 1, 2 = a + b
+    __device__ void clean(uint32_t e0, uint32_t e1, uint32_t e2, uint32_t e3) {
+        const uint32_t s0 = (e0 + (e0 >> 16)) & 3u, s1 = (e1 + (e1 >> 16)) & 3u, s2 = (e2 + (e2 >> 16)) & 3u,
+                       s3 = (e3 + (e3 >> 16)) & 3u;
+        if (max_allele) {  // (wave-uniform)
+            klo |= (1u << s0) | (1u << s1) | (1u << s2) | (1u << s3);
+            nv += 4u;
+        } else {  // ALT '.': only 0/0 is valid
+            const uint32_t z = (s0 == 0u) + (s1 == 0u) + (s2 == 0u) + (s3 == 0u);
+            klo |= z ? 1u : 0u;
+            nv += z;
+        }
+    }
+    __device__ void finish() {
+#pragma unroll
+        for (int o = kWave / 2; o > 0; o >>= 1) {
+            klo |= (uint32_t)__shfl_xor((int)klo, o);
+            khi |= (uint32_t)__shfl_xor((int)khi, o);
+        }
+        N = wave_sum(nv);
+        U = (uint32_t)(__popc(klo) + __popc(khi));
+    }
+};
+
 }  // namespace vcfxg

@@ -24,6 +24,8 @@ constexpr uint8_t kGqFull = 0xFC;     // GQ walk: a kMetaFull line for k_gq_comp
 constexpr uint8_t kHweAltComma = 1, kHweEmptyField = 2;
 // dosage HEAD walk: LineMeta::pad of a GT-only record taken on its predicted end, unswept
 constexpr uint8_t kWalkUnswept = 4;
+// concordance walk (launch_cc_walk): LineMeta::pad of a kMetaGt line whose CHROM is empty
+constexpr uint8_t kCcEmptyChrom = 8;
 
 // single-sweep index over 16 KiB wave-chunks (idx_wchunks of them): counts + the first
 // idx_pos_cap() newline offsets per chunk, then a compaction into line_end (overflow != 0:
@@ -116,6 +118,12 @@ hipError_t launch_af_walk(const char *buf, int64_t lo, int64_t hi, int64_t chunk
                           hipStream_t s, int32_t *hwe_aux_b = nullptr, const WalkTail *tail = nullptr,
                           bool dose = false, bool gt_first_walk = false, bool dose_head = false,
                           int depth = kAfDepthDefault, bool roll = false);
+// the same walk with the concordance reducer (vcfxg_cc.hip: k_af_walk<CcOp>): valid samples and
+// distinct keys of every fixed-stride record as alt_b / tot_b
+hipError_t launch_cc_walk(const char *buf, int64_t lo, int64_t hi, int64_t chunk, int mode, int64_t span0,
+                          uint64_t cap_w, uint64_t *le_b, int32_t *alt_b, int32_t *tot_b, uint32_t *rowpre_b,
+                          uint8_t *status_b, void *meta_b, uint64_t *wcount, uint32_t *wgt, unsigned *overflow,
+                          hipStream_t s);
 // AF region tail without the dense per-line arrays (vcfxg_kernels.hip):
 //   launch_af_cx       the walk's leftover slots: af_line / the general sweep, new rows' bytes
 //                      added to their walker's total (counters as k_af_complex)
@@ -321,5 +329,35 @@ hipError_t launch_sx_write(const char *buf, int64_t data_start, const uint64_t *
                            unsigned blocks, const uint32_t *mask, uint32_t nwords, uint32_t lastk, uint32_t m,
                            int stdin_mode, int seen, const uint8_t *status, const uint64_t *off, char *out,
                            hipStream_t s);
+
+// VCFX_cross_sample_concordance (vcfxg_cc.hip) over the indexed lines (*n_lines_dev of them, at
+// most n_lines_host).  launch_cc_lines: per line its status (0 no row, kCc*), valid calls (n_o),
+// distinct keys (u_o), the bytes of CHROM..ALT (rowpre) and whether it counts as a data line
+// (isdata), a wave per line; mult: per sample column (field 9 + i) how often it is selected,
+// n_mult entries (nullptr: each of the first ns once); meta: nullptr, or the concordance walk's
+// LineMeta (n_o / u_o / status hold its results): only the lines it left are parsed; counters
+// [0] concordant, [1] discordant, [2] no-genotype rows, [3] lines parsed by this kernel.
+// launch_cc_chrom: the starts of the lines that begin with "#CHROM" (the first cap of them, any
+// order; *n = their number).  ord = the exclusive scan of isdata (lines + 1 entries).
+// launch_cc_rowlen: len[place of the line] = its row's bytes, T = the reference's worker count
+// (0: record order; len zeroed beforehand); launch_cc_summary: out[0] data lines, [1] text bytes,
+// [2..5] the counters, [6] lines, [7] *fail; launch_cc_format: the rows at off[place] that end
+// within text_cap.
+enum : uint8_t { kCcSame = 1, kCcDiff = 2, kCcNoGt = 3 };
+hipError_t launch_cc_lines(const char *buf, int64_t data_start, const uint64_t *line_end, const uint64_t *n_lines_dev,
+                           uint64_t n_lines_host, int mode, uint32_t ns, const uint32_t *mult, uint32_t n_mult,
+                           const void *meta, int32_t *n_o, int32_t *u_o, uint32_t *rowpre, uint8_t *status,
+                           uint32_t *isdata, unsigned long long *counters, hipStream_t s);
+hipError_t launch_cc_chrom(const char *buf, int64_t data_start, const uint64_t *line_end, const uint64_t *n_lines_dev,
+                           uint64_t n_lines_host, uint64_t *out, uint64_t cap, unsigned long long *n, hipStream_t s);
+hipError_t launch_cc_rowlen(const uint64_t *n_lines_dev, uint64_t n_lines_host, uint64_t T, const uint64_t *ord,
+                            const uint32_t *isdata, const uint8_t *status, const int32_t *nn, const int32_t *uu,
+                            const uint32_t *rowpre, uint64_t *len, hipStream_t s);
+hipError_t launch_cc_summary(const uint64_t *n_lines_dev, const uint64_t *ord, const uint64_t *off,
+                             const unsigned long long *counters, const unsigned *fail, uint64_t *out, hipStream_t s);
+hipError_t launch_cc_format(const char *buf, int64_t data_start, const uint64_t *line_end, const uint64_t *n_lines_dev,
+                            uint64_t n_lines_host, uint64_t T, const uint64_t *ord, const uint8_t *status,
+                            const int32_t *nn, const int32_t *uu, const uint32_t *rowpre, const uint64_t *off, char *out,
+                            uint64_t text_cap, hipStream_t s);
 
 }  // namespace vcfxg

@@ -33,6 +33,11 @@ class SxParams(ctypes.Structure):
                 ("seen_chrom", ctypes.c_int)]
 
 
+class CcParams(ctypes.Structure):
+    _fields_ = [("n_samples", ctypes.c_uint32), ("mult", ctypes.c_void_p), ("n_mult", ctypes.c_uint64),
+                ("threads", ctypes.c_uint64)]
+
+
 class Criterion(ctypes.Structure):
     _fields_ = [("target", ctypes.c_int), ("op", ctypes.c_int), ("numeric", ctypes.c_int), ("value", ctypes.c_double),
                 ("key", ctypes.c_char_p), ("key_len", ctypes.c_size_t), ("str", ctypes.c_char_p),
@@ -87,6 +92,9 @@ SIGNATURES = {
     "vcfxg_inbreeding_region": (_I, [_VP, _S, _I, _VP, ctypes.POINTER(Summary)]),
     "vcfxg_inbreeding_samples": (_I, [_VP, _VP, _VP, _VP]),
     "vcfxg_sample_extract": (_I, [_VP, _U64, _U64, _VP, ctypes.POINTER(Summary)]),
+    "vcfxg_concordance_region": (_I, [_VP, _S, _I, _VP, ctypes.POINTER(Summary)]),
+    "vcfxg_concordance_totals": (_I, [_VP, _VP]),
+    "vcfxg_chrom_lines": (_I, [_VP, _S, _VP, _U64, ctypes.POINTER(_U64)]),
     "vcfxg_fetch_text_range": (_I, [_VP, _U64, _S, _VP]),
     "vcfxg_shard_cuts": (_I, [_VP, _S, _S, _I, _VP]),
     "vcfxg_comm_init": (_I, [_VP, _I, ctypes.POINTER(_VP)]),
@@ -372,6 +380,36 @@ class Engine:
             sums.append(s)
             l0 += s.n_lines
         return b"".join(text), (np.concatenate(st) if st else np.zeros(0, np.uint8)), sums
+
+    def concordance(self, data_start, mode, n_samples=0, mult=None, threads=0):
+        """VCFX_cross_sample_concordance over the lines from data_start (vcfxg_concordance_region):
+        mult = per sample column how often it is selected (None: each of the first n_samples
+        once), threads = T of the file mode's row order (0: record order).  Returns (summary,
+        totals, text): totals = (concordant, discordant, no-genotype rows, data lines); per line
+        N, U and status through lines(summary.n_lines)."""
+        import numpy as np
+        m = None if mult is None else np.ascontiguousarray(mult, np.uint32)
+        if m is not None and not len(m):
+            m = np.zeros(1, np.uint32)  # an empty selection: no column (NULL would select them all)
+        p = CcParams(int(n_samples), None if m is None else m.ctypes.data, 0 if m is None else len(m), int(threads))
+        s = Summary()
+        self._chk(self.L.vcfxg_concordance_region(self.h, data_start, int(mode), ctypes.byref(p), ctypes.byref(s)),
+                  "concordance_region")
+        t = np.zeros(4, np.uint64)
+        self._chk(self.L.vcfxg_concordance_totals(self.h, t.ctypes.data), "concordance_totals")
+        return s, tuple(int(x) for x in t), self.text(s.text_bytes)
+
+    def chrom_lines(self, data_start):
+        """start offsets of the lines from data_start that begin with '#CHROM' (vcfxg_chrom_lines)"""
+        import numpy as np
+        n = ctypes.c_uint64(0)
+        out = np.zeros(16, np.uint64)
+        self._chk(self.L.vcfxg_chrom_lines(self.h, data_start, out.ctypes.data, len(out), ctypes.byref(n)), "chrom_lines")
+        if n.value > len(out):
+            out = np.zeros(n.value, np.uint64)
+            self._chk(self.L.vcfxg_chrom_lines(self.h, data_start, out.ctypes.data, len(out), ctypes.byref(n)),
+                      "chrom_lines")
+        return out[:n.value]
 
     def haplotype_phaser(self, data_start, mode, threshold, n_samples):
         """VCFX_haplotype_phaser's parse + consecutive-variant LD (vcfxg_haplotype_phaser)"""
