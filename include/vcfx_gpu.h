@@ -452,6 +452,49 @@ int vcfxg_concordance_totals(const vcfxg_ctx *ctx, uint64_t totals[4]);
  * caller repeats the call with room for all.  The context is indexed from data_start afterwards. */
 int vcfxg_chrom_lines(vcfxg_ctx *ctx, size_t data_start, uint64_t *starts, uint64_t cap, uint64_t *n);
 
+/* ---- VCFX_duplicate_remover (a question across records: has an earlier line the same key) ------
+ * Over the indexed lines (vcfxg_index, from offset 0 for the tool): a data line is kept when no
+ * earlier data line has the same (CHROM bytes, POS integer, REF bytes, multiset of ALT tokens);
+ * ID and everything after ALT are not compared (removeDuplicates, VCFX_duplicate_remover.cpp:
+ * 182-214; processFileMmap :226-382).  Lines end at '\n' only; a '\r' is a byte of its field.
+ * Per line status (vcfxg_dedup_status):
+ *   VCFXG_DD_EMPTY   an empty line: dropped silently (:191-193, :281-284)
+ *   VCFXG_DD_HEADER  a line that starts with '#', wherever it stands: written (:194-197, :287-297)
+ *   VCFXG_DD_SHORT   a data line with fewer than four tabs: dropped, "Warning: Skipping invalid
+ *                    VCF line." (:200-205, :305-345)
+ *   VCFXG_DD_KEPT    a data line whose key no earlier line has: written
+ *   VCFXG_DD_DUP     a data line whose key an earlier line has: dropped
+ * ALT runs to the fifth tab or the line's end.  VCFXG_MODE_STDIN: POS = std::stoi of the field, 0
+ * on any exception (no digits, outside int); ALT split at every comma, empty tokens included
+ * (:111-134).  VCFXG_MODE_FILE: POS = (int)strtol from the field's first byte, whose white-space
+ * skip runs across tabs and newlines into the following fields or lines, saturating at LONG_MAX /
+ * LONG_MIN before the cast; empty ALT tokens dropped (:137-180).  Outside the domain: an input
+ * with NUL bytes, and a file-mode POS scan that reaches the input's end (the reference reads past
+ * its mapping there; this engine stops at the end).
+ * The device hashes each key (ALT as a commutative sum of token hashes: no order, no sorting),
+ * sorts (hash, line) stably and compares every line exactly with the first line of its run of
+ * equal hashes; lines that differ from it are resolved in line order against the run's kept
+ * lines, so the result does not depend on the hash.  hash_bits masks the hash before the sort.
+ * A line whose ALT ends within its first VCFXG_DD_WINDOW bytes and whose POS is 1..9 digits is
+ * parsed by one lane; every other line by a wave (general_records counts those).
+ * rows = kept lines, data_lines = kept + duplicate lines, warn_lines = SHORT lines, n_lines. */
+#define VCFXG_DD_EMPTY 0
+#define VCFXG_DD_KEPT 1
+#define VCFXG_DD_DUP 2
+#define VCFXG_DD_SHORT 3
+#define VCFXG_DD_HEADER 4
+#define VCFXG_DD_WINDOW 64
+typedef struct {
+    uint32_t hash_bits; /* 0: all 64 bits; 1..63: only the low bits (tests force collisions) */
+} vcfxg_dd_params;
+int vcfxg_dedup(vcfxg_ctx *ctx, int mode, const vcfxg_dd_params *params, vcfxg_summary *out);
+/* the statuses of lines [first, first + count) of the last vcfxg_dedup on this index (read them
+ * before another per-line call of this context writes its own); VCFXG_E_STATE without one */
+int vcfxg_dedup_status(vcfxg_ctx *ctx, uint64_t first, uint64_t count, uint8_t *status);
+/* the last vcfxg_dedup's lines per status (counts[VCFXG_DD_EMPTY .. VCFXG_DD_HEADER]) and, in
+ * counts[5], the lines the wave path parsed */
+int vcfxg_dedup_counts(const vcfxg_ctx *ctx, uint64_t counts[6]);
+
 /* ---- VCFX_haplotype_phaser (LD reuse in block phasing) ------------------
  * Over the lines from data_start (the byte after the '#CHROM' line): per line status 1 variant,
  * 4 '#' line, 3 "<10 fields", 7 invalid POS, 8 no GT in FORMAT, 0 empty (mode VCFXG_MODE_FILE:

@@ -126,6 +126,14 @@ struct vcfxg_ctx {
     // "#CHROM" line list, the summary words; the last call's totals
     DevBuf cc_mult, cc_isdata, cc_ord, cc_chrom, cc_small;
     uint64_t cc_totals[4] = {0, 0, 0, 0};
+    // VCFX_duplicate_remover: per line the five tab offsets, POS and hash, the wave pass's line
+    // list, the data flags and their scan; the (hash, line) pairs before and after the sort, its
+    // temporary storage; run heads and their scan, pending flags; the last call's counts per
+    // status and its wave-path lines
+    DevBuf dd_tabs, dd_pos, dd_hash, dd_queue, dd_isdata, dd_ord, dd_k0, dd_k1, dd_v0, dd_v1, dd_tmp, dd_hp, dd_head,
+        dd_left;
+    uint64_t dd_counts[6] = {0, 0, 0, 0, 0, 0};
+    bool dd_done = false;  // c->status holds the last vcfxg_dedup's statuses (of this index)
     // records per chain block (read when the context opens; tests cross block edges with 1, 7, 64)
     uint64_t ib_block = getenv("VCFXG_IB_BLOCK")
                             ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_IB_BLOCK"), nullptr, 10), 1), 1u << 24)

@@ -360,4 +360,29 @@ hipError_t launch_cc_format(const char *buf, int64_t data_start, const uint64_t 
                             const int32_t *nn, const int32_t *uu, const uint32_t *rowpre, const uint64_t *off, char *out,
                             uint64_t text_cap, hipStream_t s);
 
+// VCFX_duplicate_remover (vcfxg_dd.hip) over the L indexed lines.  launch_dd_key: per line its
+// status (kDdEmpty / kDdHeader / kDdShort, or undecided) and isdata (1 = undecided data line), and
+// for a data line the offsets of its first five tabs (tabs[5 li ..], the fifth = ALT's end), POS
+// and the key's hash; a lane per line over the first kDdWindow bytes, then a wave per line that
+// pass does not settle (listed in queue, L entries; counters[5] counts them); n = the input's
+// bytes.  launch_dd_gather: (hash masked to hash_bits when 1..63, line) at ord[line] (the
+// exclusive scan of isdata).  After the stable sort of the nd pairs: launch_dd_heads hp[j] = j at
+// a run's first element, else 0; head = its inclusive max scan; launch_dd_verify: heads kDdKept,
+// elements equal to their head kDdDup, the others resolved in line order against their run's kept
+// elements (left: nd zeroed bytes; counters[6] counts them).  launch_dd_count: counters[0..4] +=
+// the lines of each status.
+enum : uint8_t { kDdEmpty = 0, kDdKept = 1, kDdDup = 2, kDdShort = 3, kDdHeader = 4 };
+constexpr int kDdWindow = 64;
+hipError_t launch_dd_key(const char *buf, int64_t data_start, int64_t n, const uint64_t *line_end, uint64_t L,
+                         int stdin_mode, uint8_t *status, uint32_t *isdata, uint64_t *tabs, int32_t *pos, uint64_t *hash,
+                         uint32_t *queue, unsigned long long *counters, hipStream_t s);
+hipError_t launch_dd_gather(uint64_t L, const uint32_t *isdata, const uint64_t *ord, const uint64_t *hash,
+                            uint32_t hash_bits, uint64_t *keys, uint32_t *vals, hipStream_t s);
+hipError_t launch_dd_heads(uint64_t nd, const uint64_t *keys, uint32_t *hp, hipStream_t s);
+hipError_t launch_dd_verify(const char *buf, int64_t data_start, const uint64_t *line_end, int stdin_mode,
+                            const uint64_t *tabs, const int32_t *pos, uint64_t nd, const uint64_t *keys, const uint32_t *vals,
+                            const uint32_t *head, uint8_t *status, uint8_t *left, unsigned long long *counters,
+                            hipStream_t s);
+hipError_t launch_dd_count(uint64_t L, const uint8_t *status, unsigned long long *counters, hipStream_t s);
+
 }  // namespace vcfxg

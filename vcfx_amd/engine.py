@@ -95,6 +95,9 @@ SIGNATURES = {
     "vcfxg_concordance_region": (_I, [_VP, _S, _I, _VP, ctypes.POINTER(Summary)]),
     "vcfxg_concordance_totals": (_I, [_VP, _VP]),
     "vcfxg_chrom_lines": (_I, [_VP, _S, _VP, _U64, ctypes.POINTER(_U64)]),
+    "vcfxg_dedup": (_I, [_VP, _I, _VP, ctypes.POINTER(Summary)]),
+    "vcfxg_dedup_status": (_I, [_VP, _U64, _U64, _VP]),
+    "vcfxg_dedup_counts": (_I, [_VP, _VP]),
     "vcfxg_fetch_text_range": (_I, [_VP, _U64, _S, _VP]),
     "vcfxg_shard_cuts": (_I, [_VP, _S, _S, _I, _VP]),
     "vcfxg_comm_init": (_I, [_VP, _I, ctypes.POINTER(_VP)]),
@@ -398,6 +401,20 @@ class Engine:
         t = np.zeros(4, np.uint64)
         self._chk(self.L.vcfxg_concordance_totals(self.h, t.ctypes.data), "concordance_totals")
         return s, tuple(int(x) for x in t), self.text(s.text_bytes)
+
+    def dedup(self, mode, hash_bits=0):
+        """VCFX_duplicate_remover's decision over the indexed lines (index(0) first; vcfxg_dedup):
+        hash_bits 1..63 keeps only that many low bits of the key hash (forces collisions).  Returns
+        (summary, statuses uint8 per line: VCFXG_DD_*, counts per status + the wave-path lines)."""
+        import numpy as np
+        p = ctypes.c_uint32(int(hash_bits))  # vcfxg_dd_params
+        s = Summary()
+        self._chk(self.L.vcfxg_dedup(self.h, int(mode), ctypes.byref(p), ctypes.byref(s)), "dedup")
+        st = np.zeros(max(int(s.n_lines), 1), np.uint8)
+        self._chk(self.L.vcfxg_dedup_status(self.h, 0, s.n_lines, st.ctypes.data), "dedup_status")
+        cnt = np.zeros(6, np.uint64)
+        self._chk(self.L.vcfxg_dedup_counts(self.h, cnt.ctypes.data), "dedup_counts")
+        return s, st[:s.n_lines], tuple(int(x) for x in cnt)
 
     def chrom_lines(self, data_start):
         """start offsets of the lines from data_start that begin with '#CHROM' (vcfxg_chrom_lines)"""
