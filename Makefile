@@ -111,7 +111,8 @@ clean:
 SAN := $(B)/san
 SANFLAGS := -O1 -g -fno-omit-frame-pointer -std=c++17 -Iinclude -I$(HOST_SRC)
 SAN_HOST_SRC := tests/host_san_test.cpp $(HOST_SRC)/hostio.cpp $(HOST_SRC)/gz.cpp
-sanitize: $(SAN)/host_san_asan $(SAN)/host_san_tsan $(SAN)/core_api_asan $(SAN)/shard_tsan $(SAN)/shard_asan
+sanitize: $(SAN)/host_san_asan $(SAN)/host_san_tsan $(SAN)/core_api_asan $(SAN)/shard_tsan $(SAN)/shard_asan \
+    $(if $(wildcard tests/host_lines_test.cpp),$(SAN)/host_lines $(SAN)/host_lines_asan)
 $(SAN)/host_san_asan: $(SAN_HOST_SRC) $(wildcard $(HOST_SRC)/*.h) $(B)/libvcfx_gpu.so
 	@mkdir -p $(dir $@)
 	$(CXX) $(SANFLAGS) -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $(SAN_HOST_SRC) \
@@ -134,4 +135,16 @@ $(SAN)/shard_asan: $(SHARD_SAN_SRC) $(wildcard $(HOST_SRC)/*.h) vcfx_amd/csrc/to
 	@mkdir -p $(dir $@)
 	$(CXX) $(SANFLAGS) -Ivcfx_amd/csrc/tools -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 	    -o $@ $(SHARD_SAN_SRC) -lz -lpthread
+# the drop-ins' shared reader (emit.h) over the same stand-in, plain and under ASan + UBSan
+# (part of `sanitize` where its test program is in the tree: the other sanitizer builds do not
+# depend on it)
+HOST_LINES_SRC := tests/host_lines_test.cpp tests/shard_tsan_stub.cpp $(HOST_SRC)/hostio.cpp $(HOST_SRC)/gz.cpp
+HOST_LINES_FLAGS := $(SANFLAGS) -Ivcfx_amd/csrc/tools -DVCFX_STUB_NO_TOOL
+$(SAN)/host_lines: $(HOST_LINES_SRC) $(wildcard $(HOST_SRC)/*.h) vcfx_amd/csrc/tools/tools.h
+	@mkdir -p $(dir $@)
+	$(CXX) $(HOST_LINES_FLAGS) -o $@ $(HOST_LINES_SRC) -lz -lpthread
+$(SAN)/host_lines_asan: $(HOST_LINES_SRC) $(wildcard $(HOST_SRC)/*.h) vcfx_amd/csrc/tools/tools.h
+	@mkdir -p $(dir $@)
+	$(CXX) $(HOST_LINES_FLAGS) -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    -o $@ $(HOST_LINES_SRC) -lz -lpthread
 .PHONY: sanitize

@@ -17,9 +17,13 @@
 // Built with -DVCFX_STUB_DISCARD (build/bin/vcfx_pipe_ceiling, tools/microbench/pipe_ceiling.cpp)
 // the ingest keeps nothing: the drop-in's own stdin reader with the device stage stubbed, the
 // pipe ceiling bench.py's e2e leg quotes.
+// Built with -DVCFX_STUB_NO_TOOL (build/san/host_lines*, tests/host_lines_test.cpp) it is the
+// device under the drop-ins' shared reader: the loaded bytes, a line index over them and their
+// read-back (vcfxg_index, vcfxg_line_ends, vcfxg_fetch_lines, vcfxg_input_fetch).
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <condition_variable>
 #include <mutex>
 #include <string>
@@ -32,6 +36,8 @@ struct vcfxg_ctx {
     int device = 0;
     std::string input, text, err;
     bool ingesting = false;
+    size_t index_at = 0;         // vcfxg_index: its offset, and the end of every line from there on
+    std::vector<uint64_t> ends;
 };
 
 extern "C" {
@@ -137,6 +143,51 @@ int vcfxg_fetch_text_range(vcfxg_ctx *c, uint64_t offset, size_t n, void *host) 
     return VCFXG_OK;
 }
 
+// ---- the line index and the input read-back, for the drop-ins' shared reader (emit.h, driven by
+// tests/host_lines_test.cpp): a line ends at its '\n', a last line without one at the input's
+// end; a line's status is its length mod 4 and both of its counts are its length
+size_t vcfxg_stub_input_fetches = 0;  // calls of vcfxg_input_fetch
+uint64_t vcfxg_stub_max_block = 0;    // the most lines one vcfxg_line_ends / vcfxg_fetch_lines call asked for
+
+int vcfxg_index(vcfxg_ctx *c, size_t data_start, uint64_t *n_lines) {
+    const std::string &s = c->input;
+    c->index_at = data_start;
+    c->ends.clear();
+    for (size_t p = data_start; p < s.size();) {
+        const size_t e = std::min(s.find('\n', p), s.size());
+        c->ends.push_back(e);
+        p = e + 1;
+    }
+    *n_lines = c->ends.size();
+    return VCFXG_OK;
+}
+
+int vcfxg_line_ends(vcfxg_ctx *c, uint64_t first, uint64_t count, uint64_t *out) {
+    if (first > c->ends.size() || count > c->ends.size() - first) return VCFXG_E_ARG;
+    vcfxg_stub_max_block = std::max(vcfxg_stub_max_block, count);
+    std::copy_n(c->ends.begin() + first, count, out);
+    return VCFXG_OK;
+}
+
+int vcfxg_fetch_lines(vcfxg_ctx *c, uint64_t first, uint64_t count, int32_t *alt, int32_t *total, uint8_t *status) {
+    if (first > c->ends.size() || count > c->ends.size() - first) return VCFXG_E_ARG;
+    vcfxg_stub_max_block = std::max(vcfxg_stub_max_block, count);
+    for (uint64_t i = 0; i < count; i++) {
+        const uint64_t l = first + i, len = c->ends[l] - (l ? c->ends[l - 1] + 1 : c->index_at);
+        if (alt) alt[i] = (int32_t)len;
+        if (total) total[i] = (int32_t)len;
+        if (status) status[i] = (uint8_t)(len % 4);
+    }
+    return VCFXG_OK;
+}
+
+int vcfxg_input_fetch(vcfxg_ctx *c, uint64_t offset, size_t n, void *host) {
+    if (offset > c->input.size() || n > c->input.size() - offset) return VCFXG_E_ARG;
+    vcfxg_stub_input_fetches++;
+    memcpy(host, c->input.data() + offset, n);
+    return VCFXG_OK;
+}
+
 int vcfxg_shard_cuts(const char *data, size_t n, size_t lo, int world, uint64_t *cuts) {
     if (world < 1 || lo > n) return VCFXG_E_ARG;
     cuts[0] = lo;
@@ -199,7 +250,8 @@ std::recursive_mutex &getopt_mutex() {
 }
 }  // namespace vcfxh
 
-#ifndef VCFX_STUB_DISCARD  // (the pipe ceiling has its own main and no tool)
+// (the pipe ceiling and the reader's test, VCFX_STUB_NO_TOOL, have their own main and no tool)
+#if !defined(VCFX_STUB_DISCARD) && !defined(VCFX_STUB_NO_TOOL)
 extern "C" int vcfx_tool_main(const char *tool, int argc, char **argv, int in_fd, int out_fd, int err_fd) {
     const char *t = strrchr(tool, '/');
     t = t ? t + 1 : tool;

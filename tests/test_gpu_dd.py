@@ -288,6 +288,8 @@ def test_bgzf_input_gives_the_plain_output(tmp_path):
     assert tools.run([TOOL, "-i", str(comp)]) == want
     # inflated on the device (the host then fetches the written lines from there)
     assert _run_bin([TOOL, str(comp)], env={"VCFX_BGZF_DEVICE_MIN": "1"}) == want
+    # ... through a read-back window that moves many times
+    assert _run_bin([TOOL, str(comp)], env={"VCFX_BGZF_DEVICE_MIN": "1", "VCFX_WINDOW_BYTES": "1024"}) == want
 
 
 def test_ngpu_gives_the_unsharded_bytes(tmp_path):

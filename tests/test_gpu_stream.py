@@ -29,7 +29,8 @@ def _stdin_cases(tool):
 
 @pytest.mark.parametrize("knobs", range(len(KNOBS)))
 @pytest.mark.parametrize("tool", ["VCFX_allele_freq_calc", "VCFX_record_filter", "VCFX_genotype_query",
-                                  "VCFX_nonref_filter", "VCFX_variant_counter", "VCFX_ld_calculator"])
+                                  "VCFX_nonref_filter", "VCFX_variant_counter", "VCFX_ld_calculator",
+                                  "VCFX_missing_detector"])
 def test_golden_stdin_cases_through_a_pipe(monkeypatch, tool, knobs):
     for k, v in KNOBS[knobs].items():
         monkeypatch.setenv(k, v)

@@ -266,6 +266,8 @@ def test_bgzf_input_gives_the_plain_output(tmp_path):
     assert tools.run([TOOL, "-s", sel, "-i", str(comp)]) == want
     # inflated on the device (the host then fetches nothing but header lines)
     assert _run_bin([TOOL, "-s", sel, str(comp)], env={"VCFX_BGZF_DEVICE_MIN": "1"}) == want
+    # ... with the small read-back window of the other tools' kept lines
+    assert _run_bin([TOOL, "-s", sel, str(comp)], env={"VCFX_BGZF_DEVICE_MIN": "1", "VCFX_WINDOW_BYTES": "1024"}) == want
 
 
 @pytest.mark.parametrize("ngpu", [2, 3])

@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "emit.h"
 #include "hostio.h"
 #include "tools.h"
 
@@ -331,10 +332,7 @@ int run_stream(const Args &A, int in_fd, int out_fd, Out &err) {
     }
     // '#CHROM' lines among the records: the rows between them with the selection at that point
     std::vector<uint8_t> st(L);
-    std::vector<uint64_t> ends(L);
-    if (!gpu_ok(g, vcfxg_fetch_lines(g, 0, L, nullptr, nullptr, st.data()), "fetch_lines", err.fd) ||
-        !gpu_ok(g, vcfxg_line_ends(g, 0, L, ends.data()), "line_ends", err.fd))
-        return 1;
+    if (!gpu_ok(g, vcfxg_fetch_lines(g, 0, L, nullptr, nullptr, st.data()), "fetch_lines", err.fd)) return 1;
     std::string pend(kTextHdr);  // (written at the end, as the reference's buffer)
     uint64_t l0 = 0;
     for (uint64_t k = 0; k <= L; k++) {
@@ -346,9 +344,8 @@ int run_stream(const Args &A, int in_fd, int out_fd, Out &err) {
             if (s.text_bytes && !gpu_ok(g, vcfxg_fetch_text(g, &pend[at], s.text_bytes), "fetch", err.fd)) return 1;
         }
         if (k == L) break;
-        const uint64_t a = k ? ends[k - 1] + 1 : ds, b = ends[k];
-        std::string line(b - a, '\0');
-        if (b > a && !gpu_ok(g, vcfxg_input_fetch(g, a, b - a, &line[0]), "input_fetch", err.fd)) return 1;
+        std::string line;
+        if (!line_copy(in, g, ds, k, line, err.fd)) return 1;
         if (!rechrom(line.data(), line.data() + line.size())) return 1;
         l0 = k + 1;
     }

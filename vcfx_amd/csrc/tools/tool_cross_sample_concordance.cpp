@@ -16,6 +16,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "emit.h"
 #include "hostio.h"
 #include "tools.h"
 

@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "emit.h"
 #include "hostio.h"
 #include "tools.h"
 
@@ -43,27 +44,6 @@ const char *kHelp =
 
 const char kWarn[] = "Warning: Skipping invalid VCF line.\n";
 
-// input bytes [a, b) to out: from the host where it has them, else fetched 4 MiB at a time
-bool put_range(const Input &in, vcfxg_ctx *g, size_t a, size_t b, std::string &tmp, Out &out, int err_fd) {
-    if (a < in.host_n) {
-        const size_t e = std::min(b, in.host_n);
-        out.put(in.p + a, e - a);
-        a = e;
-    }
-    if (a < b && in.tail) {
-        out.put(in.tail + (a - in.host_n), b - a);
-        a = b;
-    }
-    while (a < b) {
-        const size_t k = std::min<size_t>(4u << 20, b - a);
-        tmp.resize(k);
-        if (!gpu_ok(g, vcfxg_input_fetch(g, a, k, &tmp[0]), "input_fetch", err_fd)) return false;
-        out.put(tmp.data(), k);
-        a += k;
-    }
-    return true;
-}
-
 bool run(const Input &in, bool stdin_mode, bool quiet, Out &out, Out &err) {
     if (in.n == 0) return true;  // (an empty file: no output at all, :243-246)
     Lines L(in, err.fd);
@@ -77,37 +57,18 @@ bool run(const Input &in, bool stdin_mode, bool quiet, Out &out, Out &err) {
     vcfxg_summary s;
     if (!gpu_ok(g, vcfxg_dedup(g, stdin_mode ? VCFXG_MODE_STDIN : VCFXG_MODE_FILE, &P, &s), "dedup", err.fd)) return false;
     phase("dedup");
-    constexpr uint64_t kBlock = 1u << 20;  // lines per fetch of statuses and line ends
-    std::vector<uint8_t> st;
-    std::vector<uint64_t> ends;
-    std::string tmp;
-    size_t ls = 0, ra = 0, rb = 0;  // the next line's start; the pending range [ra, rb)
-    for (uint64_t l0 = 0; l0 < nl; l0 += kBlock) {
-        const uint64_t k = std::min(kBlock, nl - l0);
-        st.resize(k);
-        ends.resize(k);
-        if (!gpu_ok(g, vcfxg_dedup_status(g, l0, k, st.data()), "dedup_status", err.fd) ||
-            !gpu_ok(g, vcfxg_line_ends(g, l0, k, ends.data()), "line_ends", err.fd))
-            return false;
-        for (uint64_t i = 0; i < k; i++) {
-            const size_t le = (size_t)ends[i];
-            if (st[i] == VCFXG_DD_KEPT || st[i] == VCFXG_DD_HEADER) {
-                if (rb != ls) {  // not adjacent to the pending range
-                    if (!put_range(in, g, ra, rb, tmp, out, err.fd)) return false;
-                    ra = ls;
-                }
-                rb = le;
-                if (le < in.n) rb++;  // its '\n'
-                else {  // a final line without one
-                    if (!put_range(in, g, ra, rb, tmp, out, err.fd)) return false;
-                    out.putc('\n');
-                    ra = rb;
-                }
-            }
-            ls = le + 1;
-        }
+    out.flush();
+    LineEmitter em(in.p, in.host_n, out.fd);  // (adjacent written lines leave as one range)
+    LineWalk w(in, g, em, 0, nl, err.fd, [&](uint64_t first, uint64_t count, uint8_t *st) {
+        return gpu_ok(g, vcfxg_dedup_status(g, first, count, st), "dedup_status", err.fd);
+    });
+    while (w.next()) {
+        if (w.v != VCFXG_DD_KEPT && w.v != VCFXG_DD_HEADER) continue;
+        const char *a = w.bytes();
+        if (!a) break;
+        em.line(a, a + w.len());  // (a final line without '\n' gets one)
     }
-    if (!put_range(in, g, ra, rb, tmp, out, err.fd)) return false;
+    if (!w.finish()) return false;
     phase("lines written");
     if (!quiet)
         for (uint64_t i = 0; i < s.warn_lines; i++) err.put(kWarn, sizeof kWarn - 1);

@@ -86,30 +86,20 @@ bool run_gq(const Input &in, bool stream_mode, const std::string &q, bool strict
     if (found && data_start < in.n) {
         vcfxg_ctx *g = gpu(err.fd);
         if (!g) return false;
-        uint64_t nl = 0;
         vcfxg_summary s;
         if (!load_input(g, in, err.fd) ||
             !gpu_ok(g, vcfxg_genotype_query_region(g, data_start, q.data(), q.size(), strict ? 1 : 0, 0, &s),
                     "genotype_query", err.fd))
             return false;
-        nl = s.n_lines;
-        std::vector<uint64_t> ends(nl);
-        std::vector<uint8_t> st(nl);
-        if (!gpu_ok(g, vcfxg_line_ends(g, 0, nl, ends.data()), "line_ends", err.fd) ||
-            !gpu_ok(g, vcfxg_fetch_lines(g, 0, nl, nullptr, nullptr, st.data()), "fetch_lines", err.fd))
-            return false;
-        LineSource src(in, g, em);
-        uint64_t prev = data_start;
-        for (uint64_t i = 0; i < nl; i++) {
-            const uint8_t v = st[i];
+        LineWalk w(in, g, em, data_start, s.n_lines, err.fd, line_status(g, err.fd));
+        while (w.next()) {
             const char *a = nullptr, *b = nullptr;
-            if (v == VCFXG_LINE_HEADER || v == VCFXG_LINE_ROW || v == VCFXG_LINE_WARN) {
-                a = src.at(prev, ends[i]);
+            if (w.v == VCFXG_LINE_HEADER || w.v == VCFXG_LINE_ROW || w.v == VCFXG_LINE_WARN) {
+                a = w.bytes();
                 if (!a) break;
-                b = a + (ends[i] - prev);
+                b = a + w.len();
             }
-            prev = ends[i] + 1;
-            switch (v) {
+            switch (w.v) {
             case VCFXG_LINE_HEADER: header(a, b); break;
             case VCFXG_LINE_ROW: flush_held(); em.line(a, b); break;
             case VCFXG_LINE_DROP: flush_held(); break;
@@ -126,10 +116,7 @@ bool run_gq(const Input &in, bool stream_mode, const std::string &q, bool strict
             default: break;
             }
         }
-        if (!src.ok) {
-            em.finish();
-            return gpu_ok(g, VCFXG_E_HIP, "input_fetch", err.fd);
-        }
+        if (!w.finish()) return false;
     }
     em.finish();
     if (stream_mode && !found && !quiet) err.put("Error: No #CHROM line found in VCF.\n");

@@ -166,8 +166,6 @@ bool run_ph(const Input &in, Phaser &P) {
         return true;
     }
     uint64_t V = 0, nl = 0;
-    std::vector<uint8_t> st;
-    std::vector<uint64_t> ends;
     vcfxg_ctx *g = nullptr;
     if (found && ds < in.n) {
         g = gpu(P.err.fd);
@@ -180,14 +178,10 @@ bool run_ph(const Input &in, Phaser &P) {
         phase("haplotype_phaser");
         V = s.rows;
         nl = s.n_lines;
-        st.resize(nl);
-        ends.resize(nl);
         P.text.resize(s.text_bytes);
         P.off.resize(V + 1);
         P.flags.resize(V + 1);
-        if (!gpu_ok(g, vcfxg_fetch_lines(g, 0, nl, nullptr, nullptr, st.data()), "fetch_lines", P.err.fd) ||
-            !gpu_ok(g, vcfxg_line_ends(g, 0, nl, ends.data()), "line_ends", P.err.fd) ||
-            !gpu_ok(g, vcfxg_phaser_variants(g, P.flags.data(), nullptr, P.off.data()), "phaser_variants", P.err.fd) ||
+        if (!gpu_ok(g, vcfxg_phaser_variants(g, P.flags.data(), nullptr, P.off.data()), "phaser_variants", P.err.fd) ||
             (s.text_bytes && !gpu_ok(g, vcfxg_fetch_text(g, &P.text[0], s.text_bytes), "fetch_text", P.err.fd)))
             return false;
     }
@@ -197,14 +191,13 @@ bool run_ph(const Input &in, Phaser &P) {
     if (nl) {
         // pass-through lines are read from the input (a device-only stdin through a window)
         LineEmitter dummy(in.p, in.host_n, -1);
-        LineSource src(in, g, dummy);
-        uint64_t prev = ds;
-        for (uint64_t i = 0; i < nl; i++) {
-            const uint8_t s = st[i];
+        LineWalk w(in, g, dummy, ds, nl, P.err.fd, line_status(g, P.err.fd));
+        while (w.next()) {
+            const uint8_t s = w.v;
             if (s == kHead) {
-                const char *a = src.at(prev, ends[i]);
+                const char *a = w.bytes();
                 if (!a) break;
-                const char *b = a + (ends[i] - prev);
+                const char *b = a + w.len();
                 if (b > a && b[-1] == '\r') --b;
                 P.header_line(a, b);
             } else if (s != 0) {
@@ -217,9 +210,8 @@ bool run_ph(const Input &in, Phaser &P) {
                     v++;
                 } else P.warn(s);
             }
-            prev = ends[i] + 1;
         }
-        if (!src.ok) return gpu_ok(g, VCFXG_E_HIP, "input_fetch", P.err.fd);
+        if (!w.finish()) return false;
     }
     if (P.streaming) {
         if (P.cnt) P.block(P.cnt);

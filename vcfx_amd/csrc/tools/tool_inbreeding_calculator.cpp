@@ -14,6 +14,7 @@
 #include <string_view>
 #include <vector>
 
+#include "emit.h"
 #include "hostio.h"
 #include "tools.h"
 

@@ -55,14 +55,13 @@ bool run_ld_matrix(const Input &in, bool mmap_mode, bool quiet, const std::strin
                     "ld_prepare", err.fd))
             return false;
         // every line of the region is echoed (mmap: non-empty ones)
-        std::vector<uint64_t> ends(nl);
-        if (!gpu_ok(g, vcfxg_line_ends(g, 0, nl, ends.data()), "line_ends", err.fd)) return false;
-        uint64_t prev = data_start;
-        for (uint64_t i = 0; i < nl; i++) {
-            const char *a = in.p + prev, *b = in.p + ends[i];
-            prev = ends[i] + 1;
-            if (b > a || !mmap_mode) em.line(a, b);
+        LineWalk w(in, g, em, data_start, nl, err.fd, nullptr);
+        while (w.next()) {
+            const char *a = w.bytes();
+            if (!a) break;
+            if (w.len() || !mmap_mode) em.line(a, a + w.len());
         }
+        if (!w.finish()) return false;
     }
     if (M < 2) {
         const char *t = "#LD_MATRIX_START\nNo or only one variant in the region => no pairwise LD.\n#LD_MATRIX_END\n";

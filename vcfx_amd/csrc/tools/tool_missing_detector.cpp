@@ -105,13 +105,10 @@ bool run_md(const Input &in, bool file, const char *path, bool quiet, int out_fd
     }
     // a multi-GPU rank: the summary over every rank (the fast path's message only when no rank
     // saw a '.'; a rank's own fast path writes the same bytes as its per-line pass in file mode)
-    // (the input's last byte: a shard view's tail, the host bytes, or -- a device-only input, the
-    // records of a pipe or of BGZF inflated on the device -- one byte fetched from the device)
+    // (the input's last byte: of a device-only input -- the records of a pipe or of BGZF inflated
+    // on the device -- fetched from there)
     char lastb = 0;
-    if (in.n == 0) {
-    } else if (in.tail) lastb = in.tail[in.n - in.host_n - 1];
-    else if (in.host_n == in.n) lastb = in.p[in.n - 1];
-    else if (!gpu_ok(g, vcfxg_input_fetch(g, in.n - 1, 1, &lastb), "input_fetch", err.fd)) return false;
+    if (in.n && !gpu_ok(g, input_copy(in, g, in.n - 1, in.n, &lastb), "input_fetch", err.fd)) return false;
     const bool last_nl = lastb == '\n';
     const uint64_t lines = nl - (nl && !last_nl ? 1 : 0);
     if (file && t_shard) {
@@ -123,42 +120,30 @@ bool run_md(const Input &in, bool file, const char *path, bool quiet, int out_fd
             t_shard->summary = [](const uint64_t *c) { return md_summary(c[3] == 0, c[0], c[1], c[2]); };
     }
     if (file && s.general_records == 0) {
-        // the pre-scan saw no '.' in any sample column: the input as it is
-        em.bytes(in.p + ds, in.p + in.host_n);
+        // the pre-scan saw no '.' in any sample column: the input as it is (a device-only
+        // input read back window by window)
+        LineSource src(in, g, em);
+        src.put(ds, in.n);
         em.finish();
-        if (in.tail) write_all(out_fd, in.tail, in.n - in.host_n);
-        else if (in.host_n < in.n) {  // a device-only input: read back window by window
-            LineSource src(in, g, em);
-            for (uint64_t a = in.host_n; a < in.n;) {
-                const uint64_t b = std::min<uint64_t>(in.n, a + window_bytes() - 1);
-                const char *q = src.at(a, b);
-                if (!q) break;
-                em.bytes(q, q + (b - a));
-                a = b;
-            }
-            em.finish();
-            if (!src.ok) return gpu_ok(g, VCFXG_E_HIP, "input_fetch", err.fd);
-        }
+        if (!src.ok) return gpu_ok(g, VCFXG_E_HIP, "input_fetch", err.fd);
         if (!quiet && !t_shard) err.put(md_summary(true, lines, 0, 0));
         return true;
     }
     if (nl) {
-        std::vector<uint64_t> ends(nl);
-        std::vector<uint8_t> st(nl);
-        std::vector<int32_t> is(nl), ie(nl);
-        if (!gpu_ok(g, vcfxg_line_ends(g, 0, nl, ends.data()), "line_ends", err.fd) ||
-            !gpu_ok(g, vcfxg_fetch_lines(g, 0, nl, is.data(), ie.data(), st.data()), "fetch_lines", err.fd))
-            return false;
-        LineSource src(in, g, em);
-        uint64_t prev = ds;
-        for (uint64_t i = 0; i < nl; i++) {
-            const uint8_t v = st[i];
-            const char *a = src.at(prev, ends[i]);
+        // each block's INFO spans (the alt / total arrays of vcfxg_fetch_lines) with its statuses
+        std::vector<int32_t> is, ie;
+        LineWalk w(in, g, em, ds, nl, err.fd, [&](uint64_t first, uint64_t count, uint8_t *st) {
+            is.resize(count);
+            ie.resize(count);
+            return gpu_ok(g, vcfxg_fetch_lines(g, first, count, is.data(), ie.data(), st), "fetch_lines", err.fd);
+        });
+        while (w.next()) {
+            const char *a = w.bytes();
             if (!a) break;
-            const char *b = a + (ends[i] - prev);
-            if (v == VCFXG_LINE_MISSING) {
+            const char *b = a + w.len();
+            if (w.v == VCFXG_LINE_MISSING) {
                 const char *ae = (file && b > a && b[-1] == '\r') ? b - 1 : b;
-                const char *i0 = a + is[i], *i1 = a + ie[i];
+                const char *i0 = a + is[w.k], *i1 = a + ie[w.k];
                 em.bytes(a, i0);
                 if (i1 == i0 || (i1 - i0 == 1 && *i0 == '.')) em.raw(kTag, sizeof kTag - 1);
                 else {
@@ -168,15 +153,11 @@ bool run_md(const Input &in, bool file, const char *path, bool quiet, int out_fd
                 }
                 em.bytes(i1, ae);
                 em.raw("\n", 1);
-            } else if (file) em.bytes(a, ends[i] < in.n ? b + 1 : b);  // the line's bytes as they are
+            } else if (file) em.bytes(a, w.b < in.n ? b + 1 : b);  // the line's bytes as they are
             else if (b == a) em.raw("\n", 1);
             else em.line(a, b);
-            prev = ends[i] + 1;
         }
-        if (!src.ok) {
-            em.finish();
-            return gpu_ok(g, VCFXG_E_HIP, "input_fetch", err.fd);
-        }
+        if (!w.finish()) return false;
     }
     em.finish();
     if (file && !quiet && !t_shard) err.put(md_summary(false, lines, s.data_lines, s.rows));

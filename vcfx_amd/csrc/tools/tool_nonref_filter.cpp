@@ -78,35 +78,21 @@ bool run_nr(const Input &in, bool stream_mode, int out_fd, Out &err) {
     if (found && data_start < in.n) {
         vcfxg_ctx *g = gpu(err.fd);
         if (!g) return false;
-        uint64_t nl = 0;
         vcfxg_summary s;
         if (!load_input(g, in, err.fd) ||
             !gpu_ok(g, vcfxg_nonref_filter_region(g, data_start, stream_mode ? VCFXG_MODE_STDIN : VCFXG_MODE_FILE, &s),
                     "nonref_filter", err.fd))
             return false;
-        nl = s.n_lines;
-        std::vector<uint64_t> ends(nl);
-        std::vector<uint8_t> st(nl);
-        if (!gpu_ok(g, vcfxg_line_ends(g, 0, nl, ends.data()), "line_ends", err.fd) ||
-            !gpu_ok(g, vcfxg_fetch_lines(g, 0, nl, nullptr, nullptr, st.data()), "fetch_lines", err.fd))
-            return false;
-        LineSource src(in, g, em);
-        uint64_t prev = data_start;
-        for (uint64_t i = 0; i < nl; i++) {
-            const uint8_t v = st[i];
-            if (v == VCFXG_LINE_SKIP) em.raw("\n", 1);  // an empty line
-            else if (v == VCFXG_LINE_HEADER || v == VCFXG_LINE_ROW) {
-                const char *a = src.at(prev, ends[i]);
+        LineWalk w(in, g, em, data_start, s.n_lines, err.fd, line_status(g, err.fd));
+        while (w.next()) {
+            if (w.v == VCFXG_LINE_SKIP) em.raw("\n", 1);  // an empty line
+            else if (w.v == VCFXG_LINE_HEADER || w.v == VCFXG_LINE_ROW) {
+                const char *a = w.bytes();
                 if (!a) break;
-                const char *b = a + (ends[i] - prev);
-                em.line(a, bare(a, b));
+                em.line(a, bare(a, a + w.len()));
             }  // VCFXG_LINE_DROP: every sample hom-ref
-            prev = ends[i] + 1;
         }
-        if (!src.ok) {
-            em.finish();
-            return gpu_ok(g, VCFXG_E_HIP, "input_fetch", err.fd);
-        }
+        if (!w.finish()) return false;
     }
     em.finish();
     return true;

@@ -245,16 +245,18 @@ int run_fused(const std::vector<Stage> &P, const std::string &path, int in_fd, i
         // stdin was consumed: its bytes (host part, then the device part) become the chain's stdin
         const int fd = mem_file();
         if (fd < 0) return 1;
-        write_all(fd, in.p, in.host_n);
-        if (in.host_n < in.n) {
-            vcfxg_ctx *c = g ? g : gpu(err_fd);
-            if (!c || (!g && !load_input(c, in, err_fd))) return 1;
-            std::vector<char> w((size_t)64 << 20);
-            for (uint64_t o = in.host_n; o < in.n; o += w.size()) {
-                const size_t k = (size_t)std::min<uint64_t>(w.size(), in.n - o);
-                if (!gpu_ok(c, vcfxg_input_fetch(c, o, k, w.data()), "input_fetch", err_fd)) return 1;
-                write_all(fd, w.data(), k);
-            }
+        vcfxg_ctx *c = g;
+        if (in.host_n < in.n && !c) {
+            c = gpu(err_fd);
+            if (!c || !load_input(c, in, err_fd)) return 1;
+        }
+        LineEmitter em(in.p, in.host_n, fd);
+        LineSource src(in, c, em);
+        src.put(0, in.n);
+        em.finish();
+        if (!src.ok) {
+            gpu_ok(c, VCFXG_E_HIP, "input_fetch", err_fd);
+            return 1;
         }
         lseek(fd, 0, SEEK_SET);
         *replay = fd;
@@ -282,7 +284,6 @@ int run_fused(const std::vector<Stage> &P, const std::string &path, int in_fd, i
     phase("pipe: input resident, checked");
     uint64_t nl = 0;
     std::vector<uint8_t> keep, st;
-    std::vector<uint64_t> ends;
     for (int k = 0; k < n_filters; k++) {
         const Stage &S = P[(size_t)k];
         const int mode = (k == 0 && file) ? VCFXG_MODE_FILE : VCFXG_MODE_STDIN;
@@ -301,8 +302,6 @@ int run_fused(const std::vector<Stage> &P, const std::string &path, int in_fd, i
             nl = s.n_lines;
             keep.assign(nl, 1);
             st.resize(nl);
-            ends.resize(nl);
-            if (!gpu_ok(g, vcfxg_line_ends(g, 0, nl, ends.data()), "line_ends", err_fd)) return 1;
         } else if (s.n_lines != nl) {
             return give_up();
         }
@@ -347,18 +346,17 @@ int run_fused(const std::vector<Stage> &P, const std::string &path, int in_fd, i
     // a filter last: the header, then the kept records from the device input
     LineEmitter em(in.p, in.host_n, out_fd);
     em.bytes(in.p, in.p + ds);
-    LineSource src(in, g, em);
-    uint64_t prev = ds;
-    for (uint64_t i = 0; i < nl; i++) {
-        if (keep[i]) {
-            const char *a = src.at(prev, ends[i]);
-            if (!a) break;
-            em.line(a, a + (ends[i] - prev));
-        }
-        prev = ends[i] + 1;
+    LineWalk w(in, g, em, ds, nl, err_fd, [&](uint64_t first, uint64_t count, uint8_t *v) {
+        memcpy(v, keep.data() + first, count);  // (the stages' verdicts, already on the host)
+        return true;
+    });
+    while (w.next()) {
+        if (!w.v) continue;
+        const char *a = w.bytes();
+        if (!a) break;
+        em.line(a, a + w.len());
     }
-    em.finish();
-    if (!src.ok) return gpu_ok(g, VCFXG_E_HIP, "input_fetch", err_fd) ? 0 : 1;
+    if (!w.finish()) return 1;
     phase("pipe: records written");
     return 0;
 }

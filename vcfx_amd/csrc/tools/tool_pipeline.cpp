@@ -68,7 +68,6 @@ extern "C" int vcfx_pipeline_filter_query(const char *filter, const char *logic,
     if (found && data_start < in.n) {
         vcfxg_ctx *g = gpu(err.fd);
         if (!g) return 1;
-        uint64_t nl = 0;
         vcfxg_summary s;
         std::vector<vcfxg_criterion> abi = to_abi(cs);
         if (!load_input(g, in, err.fd) ||
@@ -77,23 +76,15 @@ extern "C" int vcfx_pipeline_filter_query(const char *filter, const char *logic,
                                               strlen(query), strict, &s),
                     "filter_query", err.fd))
             return 1;
-        nl = s.n_lines;
-        std::vector<uint64_t> ends(nl);
-        std::vector<uint8_t> st(nl);
-        if (!gpu_ok(g, vcfxg_line_ends(g, 0, nl, ends.data()), "line_ends", err.fd) ||
-            !gpu_ok(g, vcfxg_fetch_lines(g, 0, nl, nullptr, nullptr, st.data()), "fetch_lines", err.fd))
-            return 1;
-        LineSource src(in, g, em);
-        uint64_t prev = data_start;
-        for (uint64_t i = 0; i < nl; i++) {
-            const uint8_t v = st[i];
+        LineWalk w(in, g, em, data_start, s.n_lines, err.fd, line_status(g, err.fd));
+        while (w.next()) {
+            const uint8_t v = w.v;
             const char *a = nullptr, *b = nullptr;
             if (v == VCFXG_LINE_HEADER || v == VCFXG_LINE_ROW || v == 7) {
-                a = src.at(prev, ends[i]);
+                a = w.bytes();
                 if (!a) break;
-                b = a + (ends[i] - prev);
+                b = a + w.len();
             }
-            prev = ends[i] + 1;
             if (v == VCFXG_LINE_HEADER) held.emplace_back(a, (size_t)(strip(a, b) - a));
             else if (v == VCFXG_LINE_ROW || v == 6 || v == 7) {
                 flush_held();
@@ -105,10 +96,7 @@ extern "C" int vcfx_pipeline_filter_query(const char *filter, const char *logic,
                 }
             }
         }
-        if (!src.ok) {
-            em.finish();
-            return gpu_ok(g, VCFXG_E_HIP, "input_fetch", err.fd) ? 0 : 1;
-        }
+        if (!w.finish()) return 1;
     }
     em.finish();
     if (!found && !gq_quiet) err.put("Error: No #CHROM line found in VCF.\n");

@@ -149,7 +149,6 @@ bool run_rf(const Input &in, bool stdin_mode, const std::vector<Criterion> &cs, 
     if (data_start >= in.n) return true;
     vcfxg_ctx *g = gpu(err.fd);
     if (!g) return false;
-    uint64_t nl = 0;
     vcfxg_summary s;
     std::vector<vcfxg_criterion> abi = to_abi(cs);
     if (!load_input(g, in, err.fd) ||
@@ -157,27 +156,16 @@ bool run_rf(const Input &in, bool stdin_mode, const std::vector<Criterion> &cs, 
                 "record_filter", err.fd))
         return false;
     phase("record_filter_region");
-    nl = s.n_lines;
-    std::vector<uint64_t> ends(nl);
-    std::vector<uint8_t> st(nl);
-    if (!gpu_ok(g, vcfxg_line_ends(g, 0, nl, ends.data()), "line_ends", err.fd) ||
-        !gpu_ok(g, vcfxg_fetch_lines(g, 0, nl, nullptr, nullptr, st.data()), "fetch_lines", err.fd))
-        return false;
-    LineSource src(in, g, em);
-    uint64_t prev = data_start;
-    for (uint64_t i = 0; i < nl; i++) {
-        const uint8_t v = st[i];
-        if (v == VCFXG_LINE_SKIP) em.raw("\n", 1);
-        else if (v == VCFXG_LINE_ROW || v == VCFXG_LINE_HEADER) {
-            const char *a = src.at(prev, ends[i]);
+    LineWalk w(in, g, em, data_start, s.n_lines, err.fd, line_status(g, err.fd));
+    while (w.next()) {
+        if (w.v == VCFXG_LINE_SKIP) em.raw("\n", 1);
+        else if (w.v == VCFXG_LINE_ROW || w.v == VCFXG_LINE_HEADER) {
+            const char *a = w.bytes();
             if (!a) break;
-            const char *b = a + (ends[i] - prev);
-            em.line(a, strip(a, b));
+            em.line(a, strip(a, a + w.len()));
         }
-        prev = ends[i] + 1;
     }
-    em.finish();
-    if (!src.ok) return gpu_ok(g, VCFXG_E_HIP, "input_fetch", err.fd);
+    if (!w.finish()) return false;
     phase("records written");
     return true;
 }

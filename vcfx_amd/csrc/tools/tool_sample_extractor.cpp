@@ -14,6 +14,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "emit.h"
 #include "hostio.h"
 #include "tools.h"
 
@@ -47,65 +48,6 @@ const char *kHelp =
 const char kWarnPre[] = "Warning: data line encountered before #CHROM => skipping.\n";
 const char kWarnShort[] = "Warning: line has <8 columns => skipping.\n";
 const char kWarnNoSamples[] = "Warning: data line with no sample columns => skipping.\n";
-
-// The input's lines in order.  The host holds bytes [0, host_n); a device-only input (a pipe
-// read without a host copy, BGZF inflated on the device, a shard view's records) keeps the rest
-// in HBM, from where a line past host_n is fetched 64 KiB at a time.
-struct Lines {
-    const Input &in;
-    int err_fd;
-    vcfxg_ctx *g = nullptr;
-    bool failed = false;
-    std::string ext;  // the current line when it is not whole on the host
-    Lines(const Input &i, int e) : in(i), err_fd(e) {}
-    bool device() {
-        if (g) return true;
-        g = gpu(err_fd);
-        if (!g || !load_input(g, in, err_fd)) {
-            failed = true;
-            return false;
-        }
-        return true;
-    }
-    // the line at pos: [ls, le) without its '\n', next = the following line's start; false at
-    // the end (or after a device error: failed)
-    bool at(size_t pos, const char *&ls, const char *&le, size_t &next) {
-        if (pos >= in.n) return false;
-        if (pos < in.host_n) {
-            const char *nl = (const char *)memchr(in.p + pos, '\n', in.host_n - pos);
-            if (nl || (in.host_n == in.n && !in.tail)) {
-                ls = in.p + pos;
-                le = nl ? nl : in.p + in.n;
-                next = nl ? (size_t)(nl - in.p) + 1 : in.n;
-                return true;
-            }
-        }
-        if (!device()) return false;
-        ext.clear();
-        size_t p = pos;
-        while (p < in.n) {
-            const size_t k = std::min<size_t>(65536, in.n - p), o = ext.size();
-            ext.resize(o + k);
-            if (!gpu_ok(g, vcfxg_input_fetch(g, p, k, &ext[o]), "input_fetch", err_fd)) {
-                failed = true;
-                return false;
-            }
-            const void *nl = memchr(ext.data() + o, '\n', k);
-            p += k;
-            if (nl) {
-                ext.resize((size_t)((const char *)nl - ext.data()));
-                ls = ext.data();
-                le = ls + ext.size();
-                next = pos + ext.size() + 1;
-                return true;
-            }
-        }
-        ls = ext.data();
-        le = ls + ext.size();
-        next = in.n;
-        return true;
-    }
-};
 
 struct Selection {
     const std::vector<std::string> &samples;
@@ -191,12 +133,9 @@ bool run_device(Lines &L, size_t start, bool stdin_mode, Selection &S, Out &out,
                 if (!extract(l, l + k) || !write_device_text(g, s.text_bytes, out, err.fd)) return false;
                 warn_lines(st, err);
             }
-            uint64_t ends[2] = {0, 0};
             const uint64_t at = l + k;
-            if (!gpu_ok(g, vcfxg_line_ends(g, at ? at - 1 : 0, at ? 2 : 1, ends), "line_ends", err.fd)) return false;
-            const uint64_t a = at ? ends[0] + 1 : start, b = at ? ends[1] : ends[0];
-            std::string line((size_t)(b - a), '\0');
-            if (b > a && !gpu_ok(g, vcfxg_input_fetch(g, a, (size_t)(b - a), &line[0]), "input_fetch", err.fd)) return false;
+            std::string line;
+            if (!line_copy(L.in, g, start, at, line, err.fd)) return false;
             S.chrom(line.data(), line.data() + line.size(), true, true, out, err);
             l = at + 1;
             continue;

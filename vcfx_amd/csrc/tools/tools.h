@@ -68,63 +68,4 @@ struct GetoptStderr {
     }
     ~GetoptStderr() { done(); }
 };
-
-// The input's lines in order.  The host holds bytes [0, host_n); a device-only input (a pipe
-// read without a host copy, BGZF inflated on the device) keeps the rest in HBM, from where the
-// header lines past host_n are fetched 64 KiB at a time.
-struct Lines {
-    const Input &in;
-    int err_fd;
-    vcfxg_ctx *g = nullptr;
-    bool failed = false;
-    std::string ext;  // the current line when it is not whole on the host
-    Lines(const Input &i, int e) : in(i), err_fd(e) {}
-    bool device() {
-        if (g) return true;
-        g = gpu(err_fd);
-        if (!g || !load_input(g, in, err_fd)) {
-            failed = true;
-            return false;
-        }
-        return true;
-    }
-    // the line at pos: [ls, le) without its '\n', next = the following line's start; false at
-    // the end (or after a device error: failed)
-    bool at(size_t pos, const char *&ls, const char *&le, size_t &next) {
-        if (pos >= in.n) return false;
-        if (pos < in.host_n) {
-            const char *nl = (const char *)memchr(in.p + pos, '\n', in.host_n - pos);
-            if (nl || in.host_n == in.n) {
-                ls = in.p + pos;
-                le = nl ? nl : in.p + in.n;
-                next = nl ? (size_t)(nl - in.p) + 1 : in.n;
-                return true;
-            }
-        }
-        if (!device()) return false;
-        ext.clear();
-        size_t p = pos;
-        while (p < in.n) {
-            const size_t k = std::min<size_t>(65536, in.n - p), o = ext.size();
-            ext.resize(o + k);
-            if (!gpu_ok(g, vcfxg_input_fetch(g, p, k, &ext[o]), "input_fetch", err_fd)) {
-                failed = true;
-                return false;
-            }
-            const void *nl = memchr(ext.data() + o, '\n', k);
-            p += k;
-            if (nl) {
-                ext.resize((size_t)((const char *)nl - ext.data()));
-                ls = ext.data();
-                le = ls + ext.size();
-                next = pos + ext.size() + 1;
-                return true;
-            }
-        }
-        ls = ext.data();
-        le = ls + ext.size();
-        next = in.n;
-        return true;
-    }
-};
 }  // namespace vcfxh
