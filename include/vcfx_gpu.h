@@ -406,6 +406,60 @@ typedef struct {
 int vcfxg_sample_extract(vcfxg_ctx *ctx, uint64_t first_line, uint64_t last_line, const vcfxg_sx_params *params,
                          vcfxg_summary *out);
 
+/* ---- VCFX_multiallelic_splitter (a value-dependent rewrite: one line per ALT allele) -----------
+ * Over the indexed lines [first_line, last_line), at most VCFXG_MS_BLOCK of them a call (read by
+ * vcfxg_open; default 65536) and no more than fit VCFXG_MS_BYTES of text (default 512 MiB; a
+ * line counts as nAlts x (its bytes + 1), and one line is always taken): the call takes the lines
+ * [first_line, first_line + n_lines) and the caller goes on from there.  A data line of >= 9
+ * fields whose ALT holds a comma is split: row a of its nAlts rows keeps fields 0-3, ALT piece a,
+ * fields 5-6 and FORMAT, and recodes INFO and every sample for that allele (recodeInfoField /
+ * recodeSample, VCFX_multiallelic_splitter.cpp:247-420).  Fields are counted as
+ * VCFXG_MODE_FILE's splitTabsView (:22-38: a line that ends in a tab has no trailing empty
+ * field) or VCFXG_MODE_STDIN's vcfx::split_tabs (it has); '\r' is never stripped.
+ * Per line status and nAlts (vcfxg_fetch_lines: status, alt):
+ *   VCFXG_MS_EMPTY   an empty line (stdin mode writes "\n", file mode nothing: the caller's)
+ *   VCFXG_MS_HEADER  a '#' line, copied by the caller
+ *   VCFXG_MS_COPY    a data line that is not split, copied by the caller; alt = 0
+ *   VCFXG_MS_SPLIT   a split line; alt = nAlts
+ * The device text (vcfxg_fetch_text_range) holds only the rows of the SPLIT lines, in line order
+ * and allele order, each with its '\n'; vcfxg_ms_line_ranges gives every line's place in it.
+ * table: the ##INFO / ##FORMAT declarations in header order, n_entries of them; the last entry
+ * of an ID wins across both sections (parseHeaderLine :226-245), and only that one counts.  The
+ * first VCFXG_MS_KEYS_LDS FORMAT keys of a line have their classes in LDS, and a table of up to
+ * VCFXG_MS_TABLE_LDS bytes (12 per ID + the ID's bytes rounded up to 4) sits there too; lines
+ * past either cap take global look-ups and are counted in general_records.
+ * rows = output rows written, data_lines = COPY + SPLIT lines, n_lines = the lines taken,
+ * text_bytes.  Outside the domain: a GT allele index of more than 9 digits, an ALT of 46,340 or
+ * more alleles (the reference's int arithmetic overflows), a line of 2 GiB or more. */
+#define VCFXG_MS_EMPTY 0
+#define VCFXG_MS_COPY 1
+#define VCFXG_MS_SPLIT 2
+#define VCFXG_MS_HEADER 4
+#define VCFXG_MS_INFO 0
+#define VCFXG_MS_FORMAT 1
+#define VCFXG_MS_NUM_OTHER 0
+#define VCFXG_MS_NUM_A 1
+#define VCFXG_MS_NUM_R 2
+#define VCFXG_MS_NUM_G 3
+#define VCFXG_MS_KEYS_LDS 32
+#define VCFXG_MS_TABLE_LDS 16384
+typedef struct {
+    const char *id;   /* the ID's bytes */
+    uint32_t id_len;
+    uint8_t section;  /* VCFXG_MS_INFO / VCFXG_MS_FORMAT */
+    uint8_t number;   /* VCFXG_MS_NUM_* */
+} vcfxg_ms_entry;
+typedef struct {
+    const vcfxg_ms_entry *table;
+    uint64_t n_entries;
+    int mode;         /* VCFXG_MODE_FILE / VCFXG_MODE_STDIN */
+} vcfxg_ms_params;
+int vcfxg_multiallelic_split(vcfxg_ctx *ctx, uint64_t first_line, uint64_t last_line, const vcfxg_ms_params *params,
+                             vcfxg_summary *out);
+/* off[i] = the text offset of the rows of line first + i of the last vcfxg_multiallelic_split's
+ * block, count + 1 entries (a line that is not split has an empty range) */
+int vcfxg_ms_line_ranges(vcfxg_ctx *ctx, uint64_t first, uint64_t count, uint64_t *off);
+
 /* ---- VCFX_cross_sample_concordance (a set question per record: its distinct genotypes) --------
  * Over the lines from data_start (the byte after the first '#CHROM' line): per record the keys of
  * parseGenotypeToId (VCFX_cross_sample_concordance.cpp:130-167: the first ':' sub-field, digits,

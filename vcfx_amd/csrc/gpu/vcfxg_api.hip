@@ -442,6 +442,7 @@ int vcfxg_index(vcfxg_ctx *c, size_t data_start, uint64_t *n_lines) {
     if (c) c->dense_pending = false;  // a new index / regions replace the pending ones
     if (!c) return VCFXG_E_ARG;
     c->dd_done = false;
+    c->ms_done = false;
     if (!c->loaded) return VCFXG_E_STATE;
     if (data_start > c->n) data_start = c->n;
     HIPCHK(c, hipSetDevice(c->device));

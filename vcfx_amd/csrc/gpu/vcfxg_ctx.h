@@ -134,6 +134,18 @@ struct vcfxg_ctx {
         dd_left;
     uint64_t dd_counts[6] = {0, 0, 0, 0, 0, 0};
     bool dd_done = false;  // c->status holds the last vcfxg_dedup's statuses (of this index)
+    // VCFX_multiallelic_splitter: the table; per line of the block its tab offsets, cost and the
+    // scans of nAlts and cost; each line's text offset; {lines taken, rows}; the last call's block;
+    // lines and text bytes per call (read when the context opens; tests make blocks of one line)
+    DevBuf ms_tab, ms_geom, ms_cost, ms_costoff, ms_rowbase, ms_lineoff, ms_small;
+    std::vector<uint32_t> ms_tab_host;
+    uint64_t ms_l0 = 0, ms_n = 0;
+    bool ms_done = false;
+    uint64_t ms_block = getenv("VCFXG_MS_BLOCK")
+                            ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_MS_BLOCK"), nullptr, 10), 1), 1u << 24)
+                            : 65536;
+    uint64_t ms_bytes = getenv("VCFXG_MS_BYTES") ? std::max<uint64_t>(strtoull(getenv("VCFXG_MS_BYTES"), nullptr, 10), 1)
+                                                 : 512ull << 20;
     // records per chain block (read when the context opens; tests cross block edges with 1, 7, 64)
     uint64_t ib_block = getenv("VCFXG_IB_BLOCK")
                             ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_IB_BLOCK"), nullptr, 10), 1), 1u << 24)

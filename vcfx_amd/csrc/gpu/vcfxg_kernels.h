@@ -385,4 +385,35 @@ hipError_t launch_dd_verify(const char *buf, int64_t data_start, const uint64_t 
                             hipStream_t s);
 hipError_t launch_dd_count(uint64_t L, const uint8_t *status, unsigned long long *counters, hipStream_t s);
 
+// VCFX_multiallelic_splitter (vcfxg_ms.hip) over n indexed lines from l0.  launch_ms_scan: per line
+// its status (kMs*), nAlts (alt[line]; 0 unless it splits), and per line of the block (i = line -
+// l0) the offsets of its nine tabs and its end (geom[kMsGeom i ..]; file mode drops one trailing
+// tab first) and its cost nAlts x (bytes + 1).  launch_ms_cut: small[0] = the lines whose summed
+// cost (costoff: the scan of cost) stays within budget, one at least; small[1] = their rows
+// (rowbase: the scan of alt from l0).  launch_ms_len / launch_ms_write: a wave per row, its bytes
+// counted (len[row]; counters[1] += the lines past a cap) or written at off[row] of out.  table:
+// entries x {ID offset in bytes, ID length, section << 8 | class} then the ID bytes, table_bytes
+// in all (a multiple of 4), one entry per ID; in LDS up to kMsTableLds bytes.  launch_ms_ranges:
+// lineoff[i] = off[rowbase[i]] (n + 1 entries), counters[0] += the data lines.
+enum : uint8_t { kMsEmpty = 0, kMsCopy = 1, kMsSplit = 2, kMsHeader = 4 };
+enum : uint32_t { kMsOther = 0, kMsA = 1, kMsR = 2, kMsG = 3 };
+enum : uint32_t { kMsInfo = 0, kMsFormat = 1 };
+constexpr uint32_t kMsKeysLds = 32;      // FORMAT keys whose classes a wave keeps in LDS; later keys: looked up per use
+constexpr uint32_t kMsTableLds = 16384;  // table bytes kept in LDS; larger: global loads
+constexpr int kMsGeom = 10;
+hipError_t launch_ms_scan(const char *buf, int64_t data_start, const uint64_t *line_end, uint64_t l0, uint64_t n,
+                          int stdin_mode, uint8_t *status, int32_t *alt, uint32_t *geom, uint64_t *cost, hipStream_t s);
+hipError_t launch_ms_cut(const uint64_t *costoff, const uint64_t *rowbase, uint64_t n, uint64_t budget, uint64_t *small,
+                         hipStream_t s);
+hipError_t launch_ms_len(const char *buf, int64_t data_start, const uint64_t *line_end, uint64_t l0, uint64_t n,
+                         int stdin_mode, const uint32_t *table, uint32_t table_bytes, uint32_t entries, uint64_t rows,
+                         const uint64_t *rowbase, const int32_t *alt, const uint32_t *geom, uint64_t *len,
+                         unsigned long long *counters, hipStream_t s);
+hipError_t launch_ms_write(const char *buf, int64_t data_start, const uint64_t *line_end, uint64_t l0, uint64_t n,
+                           int stdin_mode, const uint32_t *table, uint32_t table_bytes, uint32_t entries, uint64_t rows,
+                           const uint64_t *rowbase, const int32_t *alt, const uint32_t *geom, const uint64_t *off,
+                           char *out, hipStream_t s);
+hipError_t launch_ms_ranges(uint64_t l0, uint64_t n, const uint8_t *status, const uint64_t *rowbase,
+                            const uint64_t *rowoff, uint64_t *lineoff, unsigned long long *counters, hipStream_t s);
+
 }  // namespace vcfxg

@@ -33,6 +33,15 @@ class SxParams(ctypes.Structure):
                 ("seen_chrom", ctypes.c_int)]
 
 
+class MsEntry(ctypes.Structure):
+    _fields_ = [("id", ctypes.c_char_p), ("id_len", ctypes.c_uint32), ("section", ctypes.c_uint8),
+                ("number", ctypes.c_uint8)]
+
+
+class MsParams(ctypes.Structure):
+    _fields_ = [("table", ctypes.c_void_p), ("n_entries", ctypes.c_uint64), ("mode", ctypes.c_int)]
+
+
 class CcParams(ctypes.Structure):
     _fields_ = [("n_samples", ctypes.c_uint32), ("mult", ctypes.c_void_p), ("n_mult", ctypes.c_uint64),
                 ("threads", ctypes.c_uint64)]
@@ -98,6 +107,8 @@ SIGNATURES = {
     "vcfxg_dedup": (_I, [_VP, _I, _VP, ctypes.POINTER(Summary)]),
     "vcfxg_dedup_status": (_I, [_VP, _U64, _U64, _VP]),
     "vcfxg_dedup_counts": (_I, [_VP, _VP]),
+    "vcfxg_multiallelic_split": (_I, [_VP, _U64, _U64, _VP, ctypes.POINTER(Summary)]),
+    "vcfxg_ms_line_ranges": (_I, [_VP, _U64, _U64, _VP]),
     "vcfxg_fetch_text_range": (_I, [_VP, _U64, _S, _VP]),
     "vcfxg_shard_cuts": (_I, [_VP, _S, _S, _I, _VP]),
     "vcfxg_comm_init": (_I, [_VP, _I, ctypes.POINTER(_VP)]),
@@ -415,6 +426,28 @@ class Engine:
         cnt = np.zeros(6, np.uint64)
         self._chk(self.L.vcfxg_dedup_counts(self.h, cnt.ctypes.data), "dedup_counts")
         return s, st[:s.n_lines], tuple(int(x) for x in cnt)
+
+    def multiallelic_split(self, l0, l1, table, mode=MODE_FILE):
+        """VCFX_multiallelic_splitter over indexed lines [l0, l1) (vcfxg_multiallelic_split).  table:
+        (id bytes, section 0 INFO / 1 FORMAT, number 0 other / 1 A / 2 R / 3 G) in header order.  One
+        call takes a bounded block: returns (summary, statuses, nAlts, offsets, text) of the
+        summary's n_lines lines; text holds the rows of the split lines, line i's at
+        text[offsets[i]:offsets[i + 1]]; the caller goes on from l0 + n_lines."""
+        import numpy as np
+        ids = [bytes(t[0]) for t in table]
+        ent = (MsEntry * max(len(ids), 1))()
+        for e, i, t in zip(ent, ids, table):
+            e.id, e.id_len, e.section, e.number = i, len(i), int(t[1]), int(t[2])
+        p = MsParams(ctypes.cast(ent, ctypes.c_void_p) if ids else None, len(ids), int(mode))
+        s = Summary()
+        self._chk(self.L.vcfxg_multiallelic_split(self.h, l0, l1, ctypes.byref(p), ctypes.byref(s)),
+                  "multiallelic_split")
+        n = int(s.n_lines)
+        st, alt, off = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.int32), np.zeros(n + 1, np.uint64)
+        self._chk(self.L.vcfxg_fetch_lines(self.h, l0, n, alt.ctypes.data, None, st.ctypes.data), "fetch_lines")
+        if n:
+            self._chk(self.L.vcfxg_ms_line_ranges(self.h, l0, n, off.ctypes.data), "ms_line_ranges")
+        return s, st[:n], alt[:n], off, self.text(s.text_bytes)
 
     def chrom_lines(self, data_start):
         """start offsets of the lines from data_start that begin with '#CHROM' (vcfxg_chrom_lines)"""
