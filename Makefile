@@ -113,7 +113,8 @@ SANFLAGS := -O1 -g -fno-omit-frame-pointer -std=c++17 -Iinclude -I$(HOST_SRC)
 SAN_HOST_SRC := tests/host_san_test.cpp $(HOST_SRC)/hostio.cpp $(HOST_SRC)/gz.cpp
 sanitize: $(SAN)/host_san_asan $(SAN)/host_san_tsan $(SAN)/core_api_asan $(SAN)/shard_tsan $(SAN)/shard_asan \
     $(if $(wildcard tests/host_lines_test.cpp),$(SAN)/host_lines $(SAN)/host_lines_asan) \
-    $(if $(wildcard tests/host_ms_test.cpp),$(SAN)/host_ms_asan)
+    $(if $(wildcard tests/host_ms_test.cpp),$(SAN)/host_ms_asan) \
+    $(if $(wildcard tests/decimal_bounds_test.cpp),$(SAN)/decimal_bounds_asan)
 $(SAN)/host_san_asan: $(SAN_HOST_SRC) $(wildcard $(HOST_SRC)/*.h) $(B)/libvcfx_gpu.so
 	@mkdir -p $(dir $@)
 	$(CXX) $(SANFLAGS) -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $(SAN_HOST_SRC) \
@@ -153,4 +154,10 @@ $(SAN)/host_lines_asan: $(HOST_LINES_SRC) $(wildcard $(HOST_SRC)/*.h) vcfx_amd/c
 $(SAN)/host_ms_asan: tests/host_ms_test.cpp $(TOOL_SRC)/ms_host.h include/vcfx_gpu.h
 	@mkdir -p $(dir $@)
 	$(CXX) $(SANFLAGS) -I$(TOOL_SRC) -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
+# threshold_bounds (vcfxg_decimal.cpp: plain C++, no HIP) under ASan + UBSan: doubles' bit patterns in,
+# their two decimal rounding boundaries out (tests/test_decimal_bounds.py compares with fractions)
+$(SAN)/decimal_bounds_asan: tests/decimal_bounds_test.cpp $(GPU_SRC)/vcfxg_decimal.cpp $(GPU_SRC)/vcfxg_decimal.h
+	@mkdir -p $(dir $@)
+	$(CXX) $(SANFLAGS) -I$(GPU_SRC) -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    -o $@ tests/decimal_bounds_test.cpp $(GPU_SRC)/vcfxg_decimal.cpp
 .PHONY: sanitize

@@ -151,7 +151,12 @@ struct vcfxg_ctx {
                             ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_IB_BLOCK"), nullptr, 10), 1), 1u << 24)
                             : 65536;
     // ulps either side of the device p-value that must print the same digits (test hook: a
-    // huge value sends every exp()-derived row to the host)
+    // huge value sends every exp()-derived row to the host).  How near the p-values come to a
+    // value where the six-digit text changes, with the C library's exp (a CPU search over whole
+    // count spaces, tests/_exact_num.py hwe_nearest_boundary): the smallest distance is 4,334 ulps
+    // over every triple with N <= 100 (file mode, (2, 9, 5)); at N = 97 / 301 / 2504 it is
+    // 10,520,075 / 1,906,818 / 134,905 ulps in file mode and 8,177,671 / 7,635,856 / 263,560 on
+    // stdin.  tests/test_gpu_count_edges.py runs those triples: the device left none to the host.
     int64_t hwe_ulps = getenv("VCFXG_HWE_ULPS") ? atoll(getenv("VCFXG_HWE_ULPS")) : 16;
     // (an override is clamped to [4 KiB, 8 MiB]: the AF walk packs a walker's GT-line count in
     // 16 bits, and its line capacity 2 * chunk / hint_line + 16 stays below 2^15 for the
