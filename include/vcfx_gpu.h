@@ -460,6 +460,61 @@ int vcfxg_multiallelic_split(vcfxg_ctx *ctx, uint64_t first_line, uint64_t last_
  * block, count + 1 entries (a line that is not split has an empty range) */
 int vcfxg_ms_line_ranges(vcfxg_ctx *ctx, uint64_t first, uint64_t count, uint64_t *off);
 
+/* ---- VCFX_fasta_converter (the first transpose: a row per SAMPLE, a byte per record) ------------
+ * Over the indexed lines [first_line, last_line), at most VCFXG_FA_BLOCK of them a call (read by
+ * vcfxg_open; default 65536): the call takes the lines [first_line, first_line + n_lines) and the
+ * caller goes on from there.  Per line status (vcfxg_fasta_status):
+ *   VCFXG_FA_EMPTY    an empty line on stdin (skipped, VCFX_fasta_converter.cpp:444)
+ *   VCFXG_FA_HEADER   a '#' line, skipped wherever it stands (:311-328, :359, :446-462)
+ *   VCFXG_FA_CHROM    a line that starts with "#CHROM": the caller reads its names (fields 10 on)
+ *   VCFXG_FA_SKIPPED  stdin: a data line of fewer than 9 + n_samples fields (:480; a line that ends
+ *                     in a tab has no empty last field)
+ *   VCFXG_FA_COLUMN   a variant: VCFXG_MODE_FILE every line that does not start with '#', the empty
+ *                     ones too (:330-333); VCFXG_MODE_STDIN every other non-empty line
+ * A column's base for sample k (the k-th tab-separated field from the tenth on; file mode strips one
+ * '\r' from the line first, stdin mode none) is parseGenotype's (:198-224): N without a FORMAT key
+ * that is exactly GT, for an empty or '.'-led GT sub-field, without '/' or '|' after the first
+ * number, or when either allele's base is N; the base of allele 0 is REF when it is one byte
+ * (upper-cased as the mode does, :365 / :486), of allele k >= 1 the k-th ALT piece when it is one
+ * letter (parseAlleleBase :180-196); equal bases give that base, A/C/G/T pairs their IUPAC letter,
+ * anything else N.  A sample the line has no field for is the byte 0 (file mode's zeroed matrix).
+ * vcfxg_fasta_scan: the statuses and each line's column number within the block (n_samples: the
+ * stdin field rule); rows = columns, warn_lines = "#CHROM" lines, n_lines = the lines taken.
+ * vcfxg_fasta_begin sizes the text; vcfxg_fasta scans a block the same way, writes its columns'
+ * bases into a record-major matrix and transposes it into the text: column first_col + c of the
+ * block, sample s, is text byte row_off[s] + c' + c' / 60 with c' = first_col + c - skip[s] (columns
+ * below skip[s] are not written; skip NULL = all zero), each followed by '\n' when c' % 60 = 59 or
+ * c' + skip[s] + 1 = total_cols.  The text (vcfxg_fetch_text_range) holds the sequence lines only;
+ * the caller writes ">name\n" before each row.  general_records = the columns that left the
+ * fixed-stride path (GT first in FORMAT and every sample "a s b" with one separator and a, b in
+ * [0-9.]), rows = the block's columns, text_bytes = the size given to vcfxg_fasta_begin.
+ * Outside the domain: an allele index of more than 9 digits, a line of 2 GiB or more. */
+#define VCFXG_FA_EMPTY 0
+#define VCFXG_FA_COLUMN 1
+#define VCFXG_FA_SKIPPED 3
+#define VCFXG_FA_HEADER 4
+#define VCFXG_FA_CHROM 7
+#define VCFXG_FA_LINE 60
+#define VCFXG_FA_TILE_SAMPLES 64
+#define VCFXG_FA_TILE_COLUMNS 240
+#define VCFXG_FA_TABLE 16
+typedef struct {
+    int mode;                /* VCFXG_MODE_FILE / VCFXG_MODE_STDIN */
+    uint32_t n_samples;      /* the names these lines are parsed against */
+    uint64_t first_col;      /* the block's first column among all columns */
+    uint64_t total_cols;     /* all columns of the input */
+    const uint64_t *row_off; /* n_samples text offsets (host) */
+    const uint64_t *skip;    /* n_samples: columns before each sample's "#CHROM" line; NULL = none */
+} vcfxg_fa_params;
+int vcfxg_fasta_scan(vcfxg_ctx *ctx, uint64_t first_line, uint64_t last_line, int mode, uint32_t n_samples,
+                     vcfxg_summary *out);
+/* statuses (and, when col is not NULL, column numbers within the block: the columns before each
+ * line) of lines [first, first + count) of the last vcfxg_fasta_scan / vcfxg_fasta block */
+int vcfxg_fasta_status(vcfxg_ctx *ctx, uint64_t first, uint64_t count, uint8_t *status, uint64_t *col);
+int vcfxg_fasta_begin(vcfxg_ctx *ctx, uint64_t text_bytes);
+int vcfxg_fasta(vcfxg_ctx *ctx, uint64_t first_line, uint64_t last_line, const vcfxg_fa_params *params,
+                vcfxg_summary *out);
+
 /* ---- VCFX_cross_sample_concordance (a set question per record: its distinct genotypes) --------
  * Over the lines from data_start (the byte after the first '#CHROM' line): per record the keys of
  * parseGenotypeToId (VCFX_cross_sample_concordance.cpp:130-167: the first ':' sub-field, digits,

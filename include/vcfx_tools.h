@@ -25,6 +25,7 @@
  *   vcfx_tool_cross_sample_concordance  main, VCFX_cross_sample_concordance.cpp:359-411, 731-750
  *   vcfx_tool_duplicate_remover  run/main, VCFX_duplicate_remover.cpp:31-86, 393-399
  *   vcfx_tool_multiallelic_splitter  run/main, VCFX_multiallelic_splitter.cpp:153-204, 788-795
+ *   vcfx_tool_fasta_converter  run/main, VCFX_fasta_converter.cpp:230-258, 533-539
  *   vcfx_tool_main              the `vcfx <tool> ...` dispatch (src/vcfx_wrapper/vcfx.cpp:177-187)
  * Without a usable gfx950 device a tool that reaches the record loop writes
  * "no usable MI355X" to err_fd and returns 1 (no CPU fallback).
@@ -54,6 +55,7 @@ vcfx_entry_fn vcfx_tool_sample_extractor;
 vcfx_entry_fn vcfx_tool_cross_sample_concordance;
 vcfx_entry_fn vcfx_tool_duplicate_remover;
 vcfx_entry_fn vcfx_tool_multiallelic_splitter;
+vcfx_entry_fn vcfx_tool_fasta_converter;
 /* tool = "VCFX_<name>" (a leading path is ignored); -100 for an unknown tool */
 int vcfx_tool_main(const char *tool, int argc, char **argv, int in_fd, int out_fd, int err_fd);
 /* The same invocation over ngpu device contexts in this process (one host thread per rank;

@@ -144,6 +144,16 @@ struct vcfxg_ctx {
     uint64_t ms_block = getenv("VCFXG_MS_BLOCK")
                             ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_MS_BLOCK"), nullptr, 10), 1), 1u << 24)
                             : 65536;
+    // VCFX_fasta_converter: per line of the block its column flag, column number and FaMeta; the
+    // block's base matrix; the rows' text offsets and skipped columns; the last scan's block; the
+    // text is sized by vcfxg_fasta_begin; lines per call (read when the context opens; tests end
+    // blocks in the middle of a FASTA line with 1 and 7)
+    DevBuf fa_flag, fa_col, fa_meta, fa_M, fa_rowoff, fa_skip;
+    uint64_t fa_l0 = 0, fa_n = 0, fa_cols = 0, fa_text = 0;
+    bool fa_scanned = false, fa_begun = false;
+    uint64_t fa_block = getenv("VCFXG_FA_BLOCK")
+                            ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_FA_BLOCK"), nullptr, 10), 1), 1u << 24)
+                            : 65536;
     uint64_t ms_bytes = getenv("VCFXG_MS_BYTES") ? std::max<uint64_t>(strtoull(getenv("VCFXG_MS_BYTES"), nullptr, 10), 1)
                                                  : 512ull << 20;
     // records per chain block (read when the context opens; tests cross block edges with 1, 7, 64)

@@ -416,4 +416,36 @@ hipError_t launch_ms_write(const char *buf, int64_t data_start, const uint64_t *
 hipError_t launch_ms_ranges(uint64_t l0, uint64_t n, const uint8_t *status, const uint64_t *rowbase,
                             const uint64_t *rowoff, uint64_t *lineoff, unsigned long long *counters, hipStream_t s);
 
+// VCFX_fasta_converter (vcfxg_fa.hip) over n indexed lines from l0.  launch_fa_scan: per line its
+// status (kFa*; stdin mode's field rule uses n_samples), per line of the block (i = line - l0) the
+// column flag and FaMeta: the sample region [S, E) and ALT [alt_s, alt_e) as offsets from the line's
+// start (E excludes the file mode's '\r'; S = E = 0 for a line of fewer than ten fields), the GT
+// key's index (-1: none), the REF base (tab[0]) and the bases of ALT alleles 1..15; counters[1] +=
+// the "#CHROM" lines.  launch_fa_bases: a wave per column line writes its n_samples bases (0 for a
+// sample the line lacks) at M[col[i] * pitch ..] (col: the scan of the flags); counters[0] += the
+// lines off the fixed-stride path.  launch_fa_transpose: M rows [0, ncols) are columns first_col ..
+// of total_cols; sample s, column g goes to text[row_off[s] + c + c / 60], c = g - skip[s] (skip may
+// be null), with the '\n' after every 60th base and after the row's last.
+enum : uint8_t { kFaEmpty = 0, kFaColumn = 1, kFaSkipped = 3, kFaHeader = 4, kFaChrom = 7 };
+constexpr uint32_t kFaLine = 60;         // bases per FASTA line
+constexpr uint32_t kFaTileSamples = 64;  // the transpose tile
+constexpr uint32_t kFaTileCols = 240;
+constexpr uint32_t kFaTable = 16;        // alleles whose base the scan tabulates
+struct FaMeta {
+    uint32_t S, E, alt_s, alt_e;
+    int32_t gi;
+    uint32_t pad[3];
+    uint8_t tab[16];
+};
+static_assert(sizeof(FaMeta) == 48, "FaMeta: twelve words");
+hipError_t launch_fa_scan(const char *buf, int64_t data_start, const uint64_t *line_end, uint64_t l0, uint64_t n,
+                          int stdin_mode, uint32_t n_samples, uint8_t *status, uint32_t *flag, FaMeta *meta,
+                          unsigned long long *counters, hipStream_t s);
+hipError_t launch_fa_bases(const char *buf, int64_t data_start, const uint64_t *line_end, uint64_t l0, uint64_t n,
+                           const uint8_t *status, const uint64_t *col, const FaMeta *meta, uint32_t n_samples,
+                           uint64_t pitch, uint8_t *M, unsigned long long *counters, hipStream_t s);
+hipError_t launch_fa_transpose(const uint8_t *M, uint64_t pitch, uint64_t ncols, uint32_t n_samples, uint64_t first_col,
+                               uint64_t total_cols, const uint64_t *row_off, const uint64_t *skip, char *text,
+                               hipStream_t s);
+
 }  // namespace vcfxg

@@ -42,6 +42,11 @@ class MsParams(ctypes.Structure):
     _fields_ = [("table", ctypes.c_void_p), ("n_entries", ctypes.c_uint64), ("mode", ctypes.c_int)]
 
 
+class FaParams(ctypes.Structure):
+    _fields_ = [("mode", ctypes.c_int), ("n_samples", ctypes.c_uint32), ("first_col", ctypes.c_uint64),
+                ("total_cols", ctypes.c_uint64), ("row_off", ctypes.c_void_p), ("skip", ctypes.c_void_p)]
+
+
 class CcParams(ctypes.Structure):
     _fields_ = [("n_samples", ctypes.c_uint32), ("mult", ctypes.c_void_p), ("n_mult", ctypes.c_uint64),
                 ("threads", ctypes.c_uint64)]
@@ -109,6 +114,10 @@ SIGNATURES = {
     "vcfxg_dedup_counts": (_I, [_VP, _VP]),
     "vcfxg_multiallelic_split": (_I, [_VP, _U64, _U64, _VP, ctypes.POINTER(Summary)]),
     "vcfxg_ms_line_ranges": (_I, [_VP, _U64, _U64, _VP]),
+    "vcfxg_fasta_scan": (_I, [_VP, _U64, _U64, _I, ctypes.c_uint32, ctypes.POINTER(Summary)]),
+    "vcfxg_fasta_status": (_I, [_VP, _U64, _U64, _VP, _VP]),
+    "vcfxg_fasta_begin": (_I, [_VP, _U64]),
+    "vcfxg_fasta": (_I, [_VP, _U64, _U64, _VP, ctypes.POINTER(Summary)]),
     "vcfxg_fetch_text_range": (_I, [_VP, _U64, _S, _VP]),
     "vcfxg_shard_cuts": (_I, [_VP, _S, _S, _I, _VP]),
     "vcfxg_comm_init": (_I, [_VP, _I, ctypes.POINTER(_VP)]),
@@ -448,6 +457,36 @@ class Engine:
         if n:
             self._chk(self.L.vcfxg_ms_line_ranges(self.h, l0, n, off.ctypes.data), "ms_line_ranges")
         return s, st[:n], alt[:n], off, self.text(s.text_bytes)
+
+    def fasta_scan(self, l0, l1, n_samples, mode=MODE_FILE):
+        """VCFX_fasta_converter's statuses over indexed lines [l0, l1) (vcfxg_fasta_scan; stdin mode
+        counts a line's fields against n_samples).  One call takes a bounded block: returns (summary,
+        statuses, column numbers within the block) of the summary's n_lines lines."""
+        import numpy as np
+        s = Summary()
+        self._chk(self.L.vcfxg_fasta_scan(self.h, l0, l1, int(mode), int(n_samples), ctypes.byref(s)), "fasta_scan")
+        n = int(s.n_lines)
+        st, col = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint64)
+        if n:
+            self._chk(self.L.vcfxg_fasta_status(self.h, l0, n, st.ctypes.data, col.ctypes.data), "fasta_status")
+        return s, st[:n], col[:n]
+
+    def fasta_begin(self, text_bytes):
+        self._chk(self.L.vcfxg_fasta_begin(self.h, int(text_bytes)), "fasta_begin")
+
+    def fasta(self, l0, l1, n_samples, first_col, total_cols, row_off, skip=None, mode=MODE_FILE):
+        """the bases of the columns among indexed lines [l0, l1), transposed into the text sized by
+        fasta_begin (vcfxg_fasta): sample s, column first_col + c at row_off[s] + c' + c' // 60 with
+        c' = first_col + c - skip[s].  Returns the summary (n_lines taken, rows = columns written,
+        general_records); the text is read with text_range."""
+        import numpy as np
+        ro = np.ascontiguousarray(row_off, np.uint64)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint64)
+        p = FaParams(int(mode), int(n_samples), int(first_col), int(total_cols), ro.ctypes.data,
+                     None if sk is None else sk.ctypes.data)
+        s = Summary()
+        self._chk(self.L.vcfxg_fasta(self.h, l0, l1, ctypes.byref(p), ctypes.byref(s)), "fasta")
+        return s
 
     def chrom_lines(self, data_start):
         """start offsets of the lines from data_start that begin with '#CHROM' (vcfxg_chrom_lines)"""
