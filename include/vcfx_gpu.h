@@ -604,6 +604,57 @@ int vcfxg_dedup_status(vcfxg_ctx *ctx, uint64_t first, uint64_t count, uint8_t *
  * counts[5], the lines the wave path parsed */
 int vcfxg_dedup_counts(const vcfxg_ctx *ctx, uint64_t counts[6]);
 
+/* ---- VCFX_sorter (a permutation of the records: the lines in (CHROM, POS) order) ---------------
+ * Over the indexed lines (vcfxg_index, from offset 0 for the tool): the '#' lines in input order,
+ * then the kept data lines in key order (sortFileMmap, VCFX_sorter.cpp:321-459; sortExternal
+ * :601-674).  Lines end at '\n' only; a '\r' is a byte of its line.  Per line status
+ * (vcfxg_sort_status):
+ *   VCFXG_SRT_EMPTY   an empty line: file mode drops it, stdin mode writes "\n" among the '#' lines
+ *   VCFXG_SRT_HEADER  a line that starts with '#', wherever it stands: written first, in input order
+ *   VCFXG_SRT_PRE     file mode, a data line before the first line that starts with "#CHROM":
+ *                     dropped, "Warning: data line before #CHROM => skipping."
+ *   VCFXG_SRT_BAD     dropped, "Warning: skipping malformed line."  File mode: no tab, or a POS
+ *                     (the digits after the first tab, accumulated in a wrapping 32-bit int) of
+ *                     0; a value that wrapped negative is kept and sorts as a negative int, as in
+ *                     the compiled reference.  Stdin mode: fewer than two tabs, or a POS field std::stoi
+ *                     refuses (white space, one sign, digits; no digits or a value outside int).
+ *   VCFXG_SRT_KEPT    a data line of the output
+ * Order.  natural = 0: CHROM as unsigned bytes (a prefix before its extensions), then POS; an
+ * empty CHROM first in file mode and last in stdin mode (chromToId's 999999 there).  natural = 1:
+ * (chromToId, POS) as two ints (:43-146; names that share an id are one chromosome).  EQUAL KEYS
+ * KEEP THEIR INPUT ORDER: the reference's std::sort leaves them in whatever order its C++ library
+ * does (stable up to 16 kept lines with libstdc++), so the outputs are byte-identical when no two
+ * kept lines share a key and otherwise differ only inside runs of equal keys.
+ * The device sorts exactly for any CHROM length and any byte values (an LSD radix sort over POS,
+ * the length and CHROM's 8-byte words), then gathers the lines into the text, at most
+ * VCFXG_SRT_BLOCK bytes a call (read by vcfxg_open; default 256 MiB), one line at least:
+ * vcfxg_sort_text takes output lines [first_out_line, first_out_line + *lines_taken), each with a
+ * '\n' (a final input line without one gets it), as text bytes [0, *bytes) (vcfxg_fetch_text_range),
+ * and the caller goes on from there.  A line whose key fields end within its first
+ * VCFXG_SRT_WINDOW bytes is parsed by one lane, every other line by a wave (general_records).
+ * rows = written lines, data_lines = kept data lines, warn_lines = PRE + BAD lines, n_lines.
+ * Outside the domain: a digit run in CHROM (natural order) or a stdin-mode POS whose value the
+ * reference's own arithmetic leaves undefined. */
+#define VCFXG_SRT_EMPTY 0
+#define VCFXG_SRT_KEPT 1
+#define VCFXG_SRT_PRE 2
+#define VCFXG_SRT_BAD 3
+#define VCFXG_SRT_HEADER 4
+#define VCFXG_SRT_WINDOW 64
+typedef struct {
+    int natural; /* 0: lexicographic CHROM order; 1: -n / --natural-chr */
+} vcfxg_srt_params;
+int vcfxg_sort(vcfxg_ctx *ctx, int mode, const vcfxg_srt_params *params, vcfxg_summary *out);
+/* the statuses of lines [first, first + count) of the last vcfxg_sort on this index (read them
+ * before another per-line call of this context writes its own); VCFXG_E_STATE without one */
+int vcfxg_sort_status(vcfxg_ctx *ctx, uint64_t first, uint64_t count, uint8_t *status);
+/* the last vcfxg_sort's lines per status (counts[VCFXG_SRT_EMPTY .. VCFXG_SRT_HEADER]) and, in
+ * counts[5], the lines the wave path parsed */
+int vcfxg_sort_counts(const vcfxg_ctx *ctx, uint64_t counts[6]);
+/* the input line numbers of output lines [first, first + count) of the last vcfxg_sort */
+int vcfxg_sort_order(vcfxg_ctx *ctx, uint64_t first, uint64_t count, uint32_t *lines);
+int vcfxg_sort_text(vcfxg_ctx *ctx, uint64_t first_out_line, uint64_t *lines_taken, uint64_t *bytes);
+
 /* ---- VCFX_haplotype_phaser (LD reuse in block phasing) ------------------
  * Over the lines from data_start (the byte after the '#CHROM' line): per line status 1 variant,
  * 4 '#' line, 3 "<10 fields", 7 invalid POS, 8 no GT in FORMAT, 0 empty (mode VCFXG_MODE_FILE:

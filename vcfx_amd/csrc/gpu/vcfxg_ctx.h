@@ -134,6 +134,24 @@ struct vcfxg_ctx {
         dd_left;
     uint64_t dd_counts[6] = {0, 0, 0, 0, 0, 0};
     bool dd_done = false;  // c->status holds the last vcfxg_dedup's statuses (of this index)
+    // VCFX_sorter: per line POS, aux (chromToId or CHROM's length) and CHROM's first word, the wave
+    // pass's line list, the written flags and their scan; the (key, line) pairs of the sort and its
+    // temporary storage; per output line its bytes, their scan and its first input byte; the last
+    // call's counts per status and its wave-path lines, its written lines, which of srt_v0 / srt_v1
+    // holds the order; the offsets on the host (fetched by the first vcfxg_sort_text); text bytes
+    // per vcfxg_sort_text call (read when the context opens; tests cut between every pair of lines
+    // with 64); VCFXG_SRT_NT: bit 0 non-temporal loads, bit 1 non-temporal stores in the gather (both
+    // by default: measured 5 to 12 % faster than neither on the bench shard, DESIGN.md "Sorting")
+    DevBuf srt_pos, srt_aux, srt_w0, srt_queue, srt_written, srt_ord, srt_k0, srt_k1, srt_v0, srt_v1, srt_tmp, srt_len,
+        srt_off, srt_src;
+    uint64_t srt_counts[6] = {0, 0, 0, 0, 0, 0};
+    uint64_t srt_nw = 0;
+    bool srt_done = false, srt_in_v1 = false;
+    std::vector<uint64_t> srt_off_host;
+    uint64_t srt_block = getenv("VCFXG_SRT_BLOCK")
+                             ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_SRT_BLOCK"), nullptr, 10), 1), 1ull << 36)
+                             : 256ull << 20;
+    int srt_nt = getenv("VCFXG_SRT_NT") ? atoi(getenv("VCFXG_SRT_NT")) & 3 : 3;
     // VCFX_multiallelic_splitter: the table; per line of the block its tab offsets, cost and the
     // scans of nAlts and cost; each line's text offset; {lines taken, rows}; the last call's block;
     // lines and text bytes per call (read when the context opens; tests make blocks of one line)

@@ -448,4 +448,38 @@ hipError_t launch_fa_transpose(const uint8_t *M, uint64_t pitch, uint64_t ncols,
                                uint64_t total_cols, const uint64_t *row_off, const uint64_t *skip, char *text,
                                hipStream_t s);
 
+// VCFX_sorter (vcfxg_srt.hip) over the L indexed lines.  launch_srt_key: per line its status (kSrt*,
+// without kSrtPre), POS, aux (natural order: chromToId; lexicographic: CHROM's length) and, for the
+// lexicographic order, CHROM's first eight bytes big-endian and zero-padded (w0); a lane per line
+// whose key fields end in its first kSrtWindow bytes, then a wave per line that pass does not settle
+// (queue: L entries; counters[5] counts them); counters[6] = max(L - li) over the "#CHROM" lines.
+// launch_srt_class: file mode's data lines before the first "#CHROM" line become kSrtPre;
+// written[li] = 1 for a line of the output (header, kept; stdin mode: empty); counters[0..4] += the
+// lines per status, counters[7] = the longest kept CHROM.  launch_srt_scatter: line and first-pass
+// key of every written line at ord[line] (the exclusive scan of written): natural (id, POS) in one
+// word, lexicographic (CHROM length + 1) << 32 | POS; a header line's key is 0, a stdin-mode empty
+// CHROM's length word all ones.  launch_srt_word: keys[j] = word w of the CHROM of line vals[j] (0
+// for a header line, all ones for stdin mode's empty CHROM), shifted right by `shift` bits.  launch_srt_len: len[j] = the bytes
+// of output line j with its '\n', src[j] = its first input byte (len[nw] = 0).  launch_srt_gather:
+// output lines [first, first + k) (off: the scan of len) as bytes [0, off[first + k] - off[first])
+// of text (16 B aligned, 16 spare bytes): aligned 16 B stores only.  nt: bit 0 non-temporal loads,
+// bit 1 non-temporal stores.
+enum : uint8_t { kSrtEmpty = 0, kSrtKept = 1, kSrtPre = 2, kSrtBad = 3, kSrtHeader = 4 };
+constexpr int kSrtWindow = 64;
+hipError_t launch_srt_key(const char *buf, int64_t data_start, const uint64_t *line_end, uint64_t L, int stdin_mode,
+                          int natural, uint8_t *status, int32_t *pos, uint32_t *aux, uint64_t *w0, uint32_t *queue,
+                          unsigned long long *counters, hipStream_t s);
+hipError_t launch_srt_class(uint64_t L, int stdin_mode, int natural, uint8_t *status, const uint32_t *aux,
+                            uint32_t *written, unsigned long long *counters, hipStream_t s);
+hipError_t launch_srt_scatter(uint64_t L, int stdin_mode, int natural, const uint8_t *status, const uint32_t *written,
+                              const uint64_t *ord, const int32_t *pos, const uint32_t *aux, uint64_t *keys,
+                              uint32_t *vals, hipStream_t s);
+hipError_t launch_srt_word(const char *buf, int64_t data_start, const uint64_t *line_end, uint64_t nw, int stdin_mode,
+                           uint32_t w, uint32_t shift, const uint32_t *vals, const uint8_t *status, const uint32_t *aux,
+                           const uint64_t *w0, uint64_t *keys, hipStream_t s);
+hipError_t launch_srt_len(int64_t data_start, const uint64_t *line_end, uint64_t nw, const uint32_t *order,
+                          uint64_t *len, uint64_t *src, hipStream_t s);
+hipError_t launch_srt_gather(const char *buf, const uint64_t *off, const uint64_t *src, uint64_t first, uint64_t k,
+                             uint64_t bytes, int nt, char *text, hipStream_t s);
+
 }  // namespace vcfxg

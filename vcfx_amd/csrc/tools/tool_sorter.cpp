@@ -1,0 +1,156 @@
+// VCFX_sorter drop-in: the reference CLI (VCFX_sorter.cpp: run :676-743, main :753-761) on top of
+// vcfxg_sort.  The device decides every line, orders the written ones and gathers them into one
+// contiguous text (vcfxg_index from offset 0, vcfxg_sort, then vcfxg_sort_text block by block); the
+// host writes each block as one range and prints one warning per dropped line, in line order, from
+// the statuses.  File mode (sortFileMmap :321-459) and stdin mode (sortExternal :601-674) differ
+// in the line model and in POS (vcfx_gpu.h).
+// Equal keys: this tool sorts stably, so lines with equal (CHROM, POS) keys keep their input
+// order.  The reference's std::sort / priority_queue leave them in whatever order its C++ library
+// does (stable up to 16 kept lines with libstdc++): the outputs are byte-identical whenever no two
+// kept lines share a key, and otherwise differ only inside runs of equal keys.  -m / -t steer only
+// the reference's external merge, that is only that order: parsed and ignored.  Outside the
+// domain: a non-numeric -m (the reference dies of an uncaught exception), an unwritable -t, and
+// a CHROM digit run or stdin POS whose value the reference's own arithmetic leaves undefined.
+#include <getopt.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "emit.h"
+#include "hostio.h"
+#include "tools.h"
+
+using namespace vcfxh;
+
+namespace {
+
+// displayHelp :162-194
+const char *kHelp =
+    "VCFX_sorter: Sort a VCF by chromosome and position.\n\n"
+    "Usage:\n"
+    "  VCFX_sorter [options] [input.vcf] > output.vcf\n"
+    "  VCFX_sorter [options] < input.vcf > output.vcf\n\n"
+    "Options:\n"
+    "  -h, --help              Show help.\n"
+    "  -n, --natural-chr       Use natural chromosome order (chr1 < chr2 < chr10).\n"
+    "  -m, --max-memory <MB>   Max memory for in-memory sorting (default: 100MB).\n"
+    "                          Files larger than this use external merge sort.\n"
+    "  -t, --temp-dir <DIR>    Directory for temporary files (default: /tmp).\n\n"
+    "Description:\n"
+    "  Sorts VCF by (CHROM, POS). For small files, sorts in memory.\n"
+    "  For large files (>max-memory), uses external merge sort with\n"
+    "  temporary files, enabling sorting of files larger than RAM.\n\n"
+    "  When a file argument is provided, uses memory-mapped I/O for\n"
+    "  optimal performance (26x faster than stdin processing).\n\n"
+    "Performance:\n"
+    "  - File argument with mmap: ~30 seconds for 1GB files\n"
+    "  - Stdin processing: ~10 minutes for 1GB files\n"
+    "  - Uses pre-computed chromosome IDs for O(1) comparisons\n"
+    "  - Compact 20-byte sort keys (vs 9KB per variant)\n\n"
+    "Examples:\n"
+    "  1) Fast file sorting (recommended):\n"
+    "     VCFX_sorter input.vcf > sorted.vcf\n"
+    "  2) Stdin processing (slower):\n"
+    "     VCFX_sorter < input.vcf > sorted.vcf\n"
+    "  3) Natural chromosome order:\n"
+    "     VCFX_sorter -n input.vcf > sorted.vcf\n"
+    "  4) Large file with custom temp directory:\n"
+    "     VCFX_sorter -t /data/tmp input.vcf > sorted.vcf\n";
+
+const char kWarnPre[] = "Warning: data line before #CHROM => skipping.\n";
+const char kWarnBad[] = "Warning: skipping malformed line.\n";
+
+// one input sorted: sortFileMmap (stdin_mode false) / sortExternal
+bool run(const Input &in, bool stdin_mode, bool natural, Out &out, Out &err) {
+    if (in.n == 0) return true;  // (an empty input: no output at all, :336-339)
+    Lines L(in, err.fd);
+    if (!L.device()) return false;
+    vcfxg_ctx *g = L.g;
+    phase("input resident in HBM");
+    uint64_t nl = 0;
+    if (!gpu_ok(g, vcfxg_index(g, 0, &nl), "index", err.fd)) return false;
+    phase("index");
+    const vcfxg_srt_params P{natural ? 1 : 0};
+    vcfxg_summary s;
+    if (!gpu_ok(g, vcfxg_sort(g, stdin_mode ? VCFXG_MODE_STDIN : VCFXG_MODE_FILE, &P, &s), "sort", err.fd)) return false;
+    phase("sort");
+    for (uint64_t j = 0; j < s.rows;) {
+        uint64_t k = 0, bytes = 0;
+        if (!gpu_ok(g, vcfxg_sort_text(g, j, &k, &bytes), "sort_text", err.fd)) return false;
+        if (!write_device_text(g, bytes, out, err.fd)) return false;
+        j += k;
+    }
+    phase("lines written");
+    if (s.warn_lines) {
+        std::vector<uint8_t> st;
+        for (uint64_t l = 0; l < nl;) {
+            const uint64_t c = std::min<uint64_t>(nl - l, 1u << 20);
+            st.resize((size_t)c);
+            if (!gpu_ok(g, vcfxg_sort_status(g, l, c, st.data()), "sort_status", err.fd)) return false;
+            for (uint8_t v : st) {
+                if (v == VCFXG_SRT_PRE) err.put(kWarnPre, sizeof kWarnPre - 1);
+                else if (v == VCFXG_SRT_BAD) err.put(kWarnBad, sizeof kWarnBad - 1);
+            }
+            l += c;
+        }
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" int vcfx_tool_sorter(int argc, char **argv, int in_fd, int out_fd, int err_fd) {
+    Out out(out_fd), err(err_fd);
+    // vcfx::handle_common_flags (vcfx_core.h:57-62)
+    if (flag_present(argc, argv, "--help", "-h")) {
+        out.put(kHelp);
+        return 0;
+    }
+    if (flag_present(argc, argv, "--version", "-v")) {
+        out.put("VCFX_sorter version " VCFX_VERSION_STR "\n");
+        return 0;
+    }
+    // run :676-743
+    bool help = false, natural = false;
+    static struct option lo[] = {{"help", no_argument, nullptr, 'h'},
+                                 {"natural-chr", no_argument, nullptr, 'n'},
+                                 {"max-memory", required_argument, nullptr, 'm'},
+                                 {"temp-dir", required_argument, nullptr, 't'},
+                                 {nullptr, 0, nullptr, 0}};
+    GetoptStderr gs(err);
+    optind = 0;
+    int opt;
+    while ((opt = getopt_long(argc, argv, "hnm:t:", lo, nullptr)) != -1) {
+        if (opt == 'n') natural = true;
+        else if (opt == 'm' || opt == 't') continue;  // (the external merge's knobs: only the order of equal keys)
+        else help = true;  // -h inside a group, an unknown option (getopt's message on stderr)
+    }
+    gs.done();
+    if (help) {
+        out.put(kHelp);
+        return 0;
+    }
+    phase("start");
+    if (gs.next < argc) {  // every file sorted on its own, the outputs one after another
+        for (int i = gs.next; i < argc; i++) {
+            Input in;
+            in.gzip_ok = true;      // .vcf.gz / BGZF input is inflated (VCFX_GZIP=0: off)
+            in.bgzf_device = true;  // BGZF members inflated on the device (the lines are gathered there)
+            if (!in.open_file(argv[i])) {
+                err.put(std::string("Error: cannot open file '") + argv[i] + "'\n");
+                return 1;
+            }
+            if (!in.decompress(err.fd)) return 1;
+            if (!run(in, false, natural, out, err)) return 1;
+        }
+        return 0;
+    }
+    Input in;
+    in.gzip_ok = true;
+    in.bgzf_device = true;
+    in.read_fd(in_fd);
+    if (!in.decompress(err.fd)) return 1;
+    phase("stdin read");
+    return run(in, true, natural, out, err) ? 0 : 1;
+}

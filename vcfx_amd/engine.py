@@ -112,6 +112,11 @@ SIGNATURES = {
     "vcfxg_dedup": (_I, [_VP, _I, _VP, ctypes.POINTER(Summary)]),
     "vcfxg_dedup_status": (_I, [_VP, _U64, _U64, _VP]),
     "vcfxg_dedup_counts": (_I, [_VP, _VP]),
+    "vcfxg_sort": (_I, [_VP, _I, _VP, ctypes.POINTER(Summary)]),
+    "vcfxg_sort_status": (_I, [_VP, _U64, _U64, _VP]),
+    "vcfxg_sort_counts": (_I, [_VP, _VP]),
+    "vcfxg_sort_order": (_I, [_VP, _U64, _U64, _VP]),
+    "vcfxg_sort_text": (_I, [_VP, _U64, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "vcfxg_multiallelic_split": (_I, [_VP, _U64, _U64, _VP, ctypes.POINTER(Summary)]),
     "vcfxg_ms_line_ranges": (_I, [_VP, _U64, _U64, _VP]),
     "vcfxg_fasta_scan": (_I, [_VP, _U64, _U64, _I, ctypes.c_uint32, ctypes.POINTER(Summary)]),
@@ -435,6 +440,38 @@ class Engine:
         cnt = np.zeros(6, np.uint64)
         self._chk(self.L.vcfxg_dedup_counts(self.h, cnt.ctypes.data), "dedup_counts")
         return s, st[:s.n_lines], tuple(int(x) for x in cnt)
+
+    def sort(self, mode, natural=False):
+        """VCFX_sorter's statuses and order over the indexed lines (index(0) first; vcfxg_sort).
+        Returns (summary, statuses uint8 per line: VCFXG_SRT_*, counts per status + the wave-path
+        lines, order: the input line number of every output line)."""
+        import numpy as np
+        p = ctypes.c_int(int(bool(natural)))  # vcfxg_srt_params
+        s = Summary()
+        self._chk(self.L.vcfxg_sort(self.h, int(mode), ctypes.byref(p), ctypes.byref(s)), "sort")
+        st = np.zeros(max(int(s.n_lines), 1), np.uint8)
+        self._chk(self.L.vcfxg_sort_status(self.h, 0, s.n_lines, st.ctypes.data), "sort_status")
+        cnt = np.zeros(6, np.uint64)
+        self._chk(self.L.vcfxg_sort_counts(self.h, cnt.ctypes.data), "sort_counts")
+        order = np.zeros(max(int(s.rows), 1), np.uint32)
+        self._chk(self.L.vcfxg_sort_order(self.h, 0, s.rows, order.ctypes.data), "sort_order")
+        return s, st[:s.n_lines], tuple(int(x) for x in cnt), order[:s.rows]
+
+    def sort_text(self, first):
+        """output lines [first, first + lines) of the last sort() gathered on the device, one block
+        of at most VCFXG_SRT_BLOCK bytes (vcfxg_sort_text): (lines taken, their bytes)"""
+        k, n = ctypes.c_uint64(), ctypes.c_uint64()
+        self._chk(self.L.vcfxg_sort_text(self.h, int(first), ctypes.byref(k), ctypes.byref(n)), "sort_text")
+        return k.value, self.text_range(0, n.value)
+
+    def sorted_text(self, rows):
+        """the whole output of the last sort() (rows = its summary's rows), block after block"""
+        out, j = [], 0
+        while j < rows:
+            k, text = self.sort_text(j)
+            out.append(text)
+            j += k
+        return b"".join(out)
 
     def multiallelic_split(self, l0, l1, table, mode=MODE_FILE):
         """VCFX_multiallelic_splitter over indexed lines [l0, l1) (vcfxg_multiallelic_split).  table:
