@@ -655,6 +655,73 @@ int vcfxg_sort_counts(const vcfxg_ctx *ctx, uint64_t counts[6]);
 int vcfxg_sort_order(vcfxg_ctx *ctx, uint64_t first, uint64_t count, uint32_t *lines);
 int vcfxg_sort_text(vcfxg_ctx *ctx, uint64_t first_out_line, uint64_t *lines_taken, uint64_t *bytes);
 
+/* ---- VCFX_diff_tool (the first join of two inputs: which variant keys has only one file) --------
+ * Both files are ONE input: file 1's bytes, one '\n' when file 1 is not empty and lacks a final one,
+ * then file 2's bytes (vcfxg_ingest takes them as chunks), indexed from offset 0.  second_start is
+ * the byte where file 2 begins; the call finds the cut line itself (the first line that starts at or
+ * after it).  Lines end at '\n' only; NUL bytes and bytes >= 0x80 are ordinary bytes.  Per line
+ * status (vcfxg_diff_status; parseVariantLine, VCFX_diff_tool.cpp:214-264):
+ *   VCFXG_DF_EMPTY    an empty line
+ *   VCFXG_DF_HEADER   a line that starts with '#'
+ *   VCFXG_DF_SKIPPED  a line that, after one trailing '\r' is dropped, has fewer than four tabs, or
+ *                     whose POS field holds a byte outside 0-9 (an empty POS passes): no warning
+ *   VCFXG_DF_UNIQUE   a data line whose key is printed
+ *   VCFXG_DF_COMMON   a data line whose key the other file cancels
+ *   VCFXG_DF_REPEAT   default mode: a data line whose key an earlier line of the same file carries
+ * The key is the text CHROM:POS:REF:ALT' (generateVariantKey :168-200): POS as its bytes, ALT' =
+ * ALT (to the fifth tab or the line's end) split at every comma, empty tokens kept, the tokens in
+ * unsigned byte order (a prefix before its extensions), joined with ','.  Keys are whole strings:
+ * different fields that print the same text are the same key.
+ * assume_sorted = 0 (diffInMemoryMmap :333-404): the two files' SETS of keys; a line is UNIQUE when
+ * it is the first of its file with its key and no line of the other file has that key.  EACH SIDE
+ * IS IN INPUT ORDER OF THE KEY'S FIRST LINE; the reference prints each side in the iteration order
+ * of its C++ library's unordered_set, so the two outputs hold the same lines in another order.  The
+ * device hashes the key text, sorts (hash, line) stably and compares every line exactly with the
+ * first line of its run; lines that differ are resolved in line order, so the result does not
+ * depend on the hash.  hash_bits masks the hash before the sort.
+ * assume_sorted = 1 (diffStreamingMmap :409-506): the two-pointer walk over both files' data lines
+ * under compareKeys (:312-328): CHROM as unsigned bytes, or with natural = 1 compareChromNatural
+ * (:269-307: a prefix of exactly chr / Chr / CHR dropped, names with a decimal digit prefix first and
+ * among themselves by its value, then the rest as bytes); POS as an integer; REF bytes; the raw ALT
+ * bytes.  Less: file 1's key is reported; greater: file 2's; equal: neither; what is left is
+ * reported; each side in file order, repeats kept.  When both files are non-decreasing the walk is
+ * a multiset difference, decided per line by binary searches (VCFXG_DF_PATH_BOUNDS); otherwise the
+ * device runs the loop itself, one wave, at most VCFXG_DF_WALK_STEPS steps a launch (read by
+ * vcfxg_open; default 2^20) with its pointers in device memory (VCFXG_DF_PATH_WALK).  Outside the
+ * domain: a POS or a natural-order digit prefix of more than 18 digits (the reference's long
+ * arithmetic overflows).  natural is read only with assume_sorted.
+ * A line whose fifth tab lies within its first VCFXG_DF_WINDOW bytes (or that is no longer than
+ * that) is parsed by one lane; every other line by a wave (general_records counts those).
+ * rows = unique lines of both sides, data_lines, warn_lines = skipped lines, n_lines.
+ * vcfxg_diff_counts: unique lines of file 1 and of file 2, data lines of file 1 and of file 2,
+ * skipped lines, the lines the wave path parsed, the path taken (VCFXG_DF_PATH_*), the cut line.
+ * vcfxg_diff_text: keys [first_out, first_out + *taken) of one side's output (side 0: file 1), each
+ * with its '\n', as text bytes [0, *bytes) (vcfxg_fetch_text_range): at most VCFXG_DF_BLOCK bytes a
+ * call (read by vcfxg_open; default 256 MiB), one key at least; the caller goes on from
+ * first_out + *taken. */
+#define VCFXG_DF_EMPTY 0
+#define VCFXG_DF_COMMON 1
+#define VCFXG_DF_UNIQUE 2
+#define VCFXG_DF_SKIPPED 3
+#define VCFXG_DF_HEADER 4
+#define VCFXG_DF_REPEAT 5
+#define VCFXG_DF_WINDOW 64
+#define VCFXG_DF_PATH_HASH 0
+#define VCFXG_DF_PATH_BOUNDS 1
+#define VCFXG_DF_PATH_WALK 2
+typedef struct {
+    uint64_t second_start; /* the byte where file 2 begins */
+    int assume_sorted;     /* -s / --assume-sorted */
+    int natural;           /* -n / --natural-chr (with assume_sorted) */
+    uint32_t hash_bits;    /* 0: all 64 bits; 1..63: only the low bits (tests force collisions) */
+} vcfxg_df_params;
+int vcfxg_diff(vcfxg_ctx *ctx, const vcfxg_df_params *params, vcfxg_summary *out);
+/* the statuses of lines [first, first + count) of the last vcfxg_diff on this index (read them
+ * before another per-line call of this context writes its own); VCFXG_E_STATE without one */
+int vcfxg_diff_status(vcfxg_ctx *ctx, uint64_t first, uint64_t count, uint8_t *status);
+int vcfxg_diff_counts(const vcfxg_ctx *ctx, uint64_t counts[8]);
+int vcfxg_diff_text(vcfxg_ctx *ctx, int side, uint64_t first_out, uint64_t *taken, uint64_t *bytes);
+
 /* ---- VCFX_haplotype_phaser (LD reuse in block phasing) ------------------
  * Over the lines from data_start (the byte after the '#CHROM' line): per line status 1 variant,
  * 4 '#' line, 3 "<10 fields", 7 invalid POS, 8 no GT in FORMAT, 0 empty (mode VCFXG_MODE_FILE:

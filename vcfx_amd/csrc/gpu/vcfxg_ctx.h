@@ -152,6 +152,28 @@ struct vcfxg_ctx {
                              ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_SRT_BLOCK"), nullptr, 10), 1), 1ull << 36)
                              : 256ull << 20;
     int srt_nt = getenv("VCFXG_SRT_NT") ? atoi(getenv("VCFXG_SRT_NT")) & 3 : 3;
+    // VCFX_diff_tool: per line the five tab offsets, the key's length and its scan, ALT's token count,
+    // POS and CHROM's natural-order parts, the key's hash, the data flags and their scan, the wave
+    // passes' line list; the key text; the data lines in line order; the (hash, line) pairs of the
+    // sort and its temporary storage, run heads and their scan, each element's class, each class's
+    // first file-2 element, pending flags; the walk's two pointers; the unique flags and their scan,
+    // per unique line its bytes, their scan and its key's place (the gather is the sorter's); the
+    // summary words; the last call's counts, its unique lines in all and of file 1; the offsets on
+    // the host (fetched by the first vcfxg_diff_text); text bytes per vcfxg_diff_text call and steps
+    // per launch of the serial walk (read when the context opens; tests use 64 and 7)
+    DevBuf df_tabs, df_klen, df_koff, df_ntok, df_posv, df_natv, df_nsuf, df_hash, df_isdata, df_ord, df_queue, df_ktext,
+        df_line, df_k0, df_k1, df_v0, df_v1, df_tmp, df_hp, df_head, df_rep, df_first2, df_left, df_state, df_uflag, df_uord,
+        df_len, df_off, df_src, df_sum;
+    uint64_t df_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t df_nu = 0, df_nu1 = 0;
+    bool df_done = false;
+    std::vector<uint64_t> df_off_host;
+    uint64_t df_block = getenv("VCFXG_DF_BLOCK")
+                            ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_DF_BLOCK"), nullptr, 10), 1), 1ull << 36)
+                            : 256ull << 20;
+    uint64_t df_walk_steps = getenv("VCFXG_DF_WALK_STEPS")
+                                 ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_DF_WALK_STEPS"), nullptr, 10), 1), 1ull << 24)
+                                 : 1ull << 20;
     // VCFX_multiallelic_splitter: the table; per line of the block its tab offsets, cost and the
     // scans of nAlts and cost; each line's text offset; {lines taken, rows}; the last call's block;
     // lines and text bytes per call (read when the context opens; tests make blocks of one line)

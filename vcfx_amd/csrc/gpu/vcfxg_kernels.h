@@ -482,4 +482,60 @@ hipError_t launch_srt_len(int64_t data_start, const uint64_t *line_end, uint64_t
 hipError_t launch_srt_gather(const char *buf, const uint64_t *off, const uint64_t *src, uint64_t first, uint64_t k,
                              uint64_t bytes, int nt, char *text, hipStream_t s);
 
+// VCFX_diff_tool (vcfxg_df.hip) over the L indexed lines of two files in one text; the lines from
+// `cut` on are file 2's (launch_df_cut: counters[7] = the first line that starts at or after
+// second_start).  launch_df_key: per line its status (kDfEmpty / kDfHeader / kDfSkipped, or kDfData:
+// undecided) and isdata, and for a data line the offsets of its first five tabs (the fifth = ALT's
+// end: the tab or the line's end without one '\r'), the key's length, ALT's token count, POS as an
+// integer and CHROM's natural-order parts (the digit prefix's value after the "chr" prefix, -1
+// without one, and where the rest of the name begins); a lane per line whose key fields end in its
+// first kDfWindow bytes, then a wave per line that pass does not settle (queue: L entries;
+// counters[5] counts them); counters[4] += the skipped lines.  launch_df_text: every data line's
+// key text CHROM:POS:REF:ALT' at koff[line] of ktext (ALT' = ALT's tokens in byte order), its hash,
+// and line[ord[line]] = line (ord: the exclusive scan of isdata); queue as above, counters[9].
+// Default mode, after the stable sort of the nd (hash, line) pairs and the run heads
+// (launch_dd_heads, max scan): launch_df_classes: rep[j] = the first element of j's run with j's
+// key (exact compares; left: nd zeroed bytes, counters[6] the elements that differ from their head),
+// first2[rep] = the class's first element of file 2, then each line's status.  Sorted mode:
+// launch_df_ordered: counters[8] = 1 when a data line compares greater than the next one of its
+// file; launch_df_bounds: each data line's status from three binary searches; launch_df_walk: at
+// most `steps` steps of the two-pointer loop from state[0..1] (one wave); launch_df_drain: the lines
+// the loop left are unique.  launch_df_flag: uflag[line] = 1 for a unique line (uflag[L] = 0);
+// launch_df_place: len / src of every unique line at uord[line] (len[U] = 0) for launch_srt_gather;
+// launch_df_sum: sum[0..7] = vcfxg_diff_counts' words but the path.
+enum : uint8_t { kDfEmpty = 0, kDfCommon = 1, kDfUnique = 2, kDfSkipped = 3, kDfHeader = 4, kDfRepeat = 5, kDfData = 6 };
+constexpr int kDfWindow = 64;
+struct DfLines {
+    const char *buf;
+    int64_t data_start;
+    const uint64_t *line_end;
+    uint64_t L;
+    uint8_t *status;
+    uint32_t *isdata, *ntok;
+    uint64_t *tabs, *klen, *nsuf;
+    int64_t *posv, *natv;
+};
+hipError_t launch_df_cut(const uint64_t *line_end, int64_t data_start, uint64_t L, uint64_t second_start,
+                         unsigned long long *counters, hipStream_t s);
+hipError_t launch_df_key(const DfLines &D, int natural, uint32_t *queue, unsigned long long *counters, hipStream_t s);
+hipError_t launch_df_text(const DfLines &D, const uint64_t *ord, const uint64_t *koff, char *ktext, uint64_t *hash,
+                          uint32_t *line, uint32_t *queue, unsigned long long *counters, hipStream_t s);
+hipError_t launch_df_pairs(uint64_t nd, const uint32_t *line, const uint64_t *hash, uint32_t hash_bits, uint64_t *keys,
+                           uint32_t *vals, hipStream_t s);
+hipError_t launch_df_classes(const char *ktext, const uint64_t *koff, const uint64_t *klen, uint64_t nd, const uint64_t *keys,
+                             const uint32_t *vals, const uint32_t *head, uint32_t *rep, uint32_t *first2, uint8_t *left,
+                             uint8_t *status, unsigned long long *counters, hipStream_t s);
+hipError_t launch_df_ordered(const DfLines &D, int natural, const uint32_t *line, uint64_t n1, uint64_t nd,
+                             unsigned long long *counters, hipStream_t s);
+hipError_t launch_df_bounds(const DfLines &D, int natural, const uint32_t *line, uint64_t n1, uint64_t nd, hipStream_t s);
+hipError_t launch_df_walk(const DfLines &D, int natural, const uint32_t *line, uint64_t n1, uint64_t nd, uint64_t steps,
+                          uint64_t *state, hipStream_t s);
+hipError_t launch_df_drain(const uint32_t *line, uint64_t n1, uint64_t nd, const uint64_t *state, uint8_t *status,
+                           hipStream_t s);
+hipError_t launch_df_flag(uint64_t L, const uint8_t *status, uint32_t *uflag, hipStream_t s);
+hipError_t launch_df_place(uint64_t L, const uint32_t *uflag, const uint64_t *uord, const uint64_t *koff,
+                           const uint64_t *klen, uint64_t *len, uint64_t *src, hipStream_t s);
+hipError_t launch_df_sum(uint64_t L, const uint64_t *ord, const uint64_t *uord, const unsigned long long *counters,
+                         uint64_t *sum, hipStream_t s);
+
 }  // namespace vcfxg

@@ -31,5 +31,6 @@ extern "C" int vcfx_tool_main(const char *tool, int argc, char **argv, int in_fd
     if (!strcmp(t, "VCFX_multiallelic_splitter")) return vcfx_tool_multiallelic_splitter(argc, argv, in_fd, out_fd, err_fd);
     if (!strcmp(t, "VCFX_fasta_converter")) return vcfx_tool_fasta_converter(argc, argv, in_fd, out_fd, err_fd);
     if (!strcmp(t, "VCFX_sorter")) return vcfx_tool_sorter(argc, argv, in_fd, out_fd, err_fd);
+    if (!strcmp(t, "VCFX_diff_tool")) return vcfx_tool_diff_tool(argc, argv, in_fd, out_fd, err_fd);
     return -100;
 }

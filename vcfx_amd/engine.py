@@ -47,6 +47,11 @@ class FaParams(ctypes.Structure):
                 ("total_cols", ctypes.c_uint64), ("row_off", ctypes.c_void_p), ("skip", ctypes.c_void_p)]
 
 
+class DfParams(ctypes.Structure):
+    _fields_ = [("second_start", ctypes.c_uint64), ("assume_sorted", ctypes.c_int), ("natural", ctypes.c_int),
+                ("hash_bits", ctypes.c_uint32)]
+
+
 class CcParams(ctypes.Structure):
     _fields_ = [("n_samples", ctypes.c_uint32), ("mult", ctypes.c_void_p), ("n_mult", ctypes.c_uint64),
                 ("threads", ctypes.c_uint64)]
@@ -117,6 +122,10 @@ SIGNATURES = {
     "vcfxg_sort_counts": (_I, [_VP, _VP]),
     "vcfxg_sort_order": (_I, [_VP, _U64, _U64, _VP]),
     "vcfxg_sort_text": (_I, [_VP, _U64, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "vcfxg_diff": (_I, [_VP, _VP, ctypes.POINTER(Summary)]),
+    "vcfxg_diff_status": (_I, [_VP, _U64, _U64, _VP]),
+    "vcfxg_diff_counts": (_I, [_VP, _VP]),
+    "vcfxg_diff_text": (_I, [_VP, _I, _U64, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "vcfxg_multiallelic_split": (_I, [_VP, _U64, _U64, _VP, ctypes.POINTER(Summary)]),
     "vcfxg_ms_line_ranges": (_I, [_VP, _U64, _U64, _VP]),
     "vcfxg_fasta_scan": (_I, [_VP, _U64, _U64, _I, ctypes.c_uint32, ctypes.POINTER(Summary)]),
@@ -469,6 +478,40 @@ class Engine:
         out, j = [], 0
         while j < rows:
             k, text = self.sort_text(j)
+            out.append(text)
+            j += k
+        return b"".join(out)
+
+    def diff(self, second_start, assume_sorted=False, natural=False, hash_bits=0):
+        """VCFX_diff_tool over the indexed lines of two files loaded as one text (file 1, a newline if
+        it lacks its last one, file 2; index(0) first; vcfxg_diff): second_start = the byte where
+        file 2 begins.  Returns (summary, statuses uint8 per line: VCFXG_DF_*, counts: unique lines
+        of file 1 and 2, data lines of file 1 and 2, skipped lines, wave-path lines, the path taken,
+        the cut line)."""
+        import numpy as np
+        p = DfParams(int(second_start), int(bool(assume_sorted)), int(bool(natural)), int(hash_bits))
+        s = Summary()
+        self._chk(self.L.vcfxg_diff(self.h, ctypes.byref(p), ctypes.byref(s)), "diff")
+        st = np.zeros(max(int(s.n_lines), 1), np.uint8)
+        self._chk(self.L.vcfxg_diff_status(self.h, 0, s.n_lines, st.ctypes.data), "diff_status")
+        cnt = np.zeros(8, np.uint64)
+        self._chk(self.L.vcfxg_diff_counts(self.h, cnt.ctypes.data), "diff_counts")
+        return s, st[:s.n_lines], tuple(int(x) for x in cnt)
+
+    def diff_text(self, side, first):
+        """keys [first, first + taken) of one side (0: file 1) of the last diff(), each with its
+        newline, one block of at most VCFXG_DF_BLOCK bytes (vcfxg_diff_text): (keys taken, bytes)"""
+        k, n = ctypes.c_uint64(), ctypes.c_uint64()
+        self._chk(self.L.vcfxg_diff_text(self.h, int(side), int(first), ctypes.byref(k), ctypes.byref(n)), "diff_text")
+        return k.value, self.text_range(0, n.value)
+
+    def diffed_text(self, side):
+        """one side's whole output of the last diff(), block after block"""
+        cnt = (ctypes.c_uint64 * 8)()
+        self._chk(self.L.vcfxg_diff_counts(self.h, ctypes.cast(cnt, ctypes.c_void_p)), "diff_counts")
+        out, j = [], 0
+        while j < cnt[int(side)]:
+            k, text = self.diff_text(side, j)
             out.append(text)
             j += k
         return b"".join(out)
