@@ -722,6 +722,73 @@ int vcfxg_diff_status(vcfxg_ctx *ctx, uint64_t first, uint64_t count, uint8_t *s
 int vcfxg_diff_counts(const vcfxg_ctx *ctx, uint64_t counts[8]);
 int vcfxg_diff_text(vcfxg_ctx *ctx, int side, uint64_t first_out, uint64_t *taken, uint64_t *bytes);
 
+/* ---- VCFX_merger (the first join of K inputs: their lines in key order) -------------------------
+ * The files are ONE input: every opened file in list order, each followed by one '\n' when it is
+ * not empty and lacks a final one (vcfxg_ingest takes them as chunks), indexed from offset 0.
+ * file_start holds n_files + 1 non-decreasing byte offsets: where each file begins, then the
+ * text's size; the call finds each file's first line itself.  Lines end at '\n' only; '\r', NUL
+ * and bytes >= 0x80 are ordinary bytes.  Per line status (vcfxg_merge_status):
+ *   VCFXG_MG_EMPTY    an empty line: dropped
+ *   VCFXG_MG_KEPT     a data line of the output
+ *   VCFXG_MG_BAD      a line that does not start with '#' and has fewer than two tabs, or whose POS
+ *                     (the bytes between the first two tabs) std::stol refuses: white space, one
+ *                     sign, at least one decimal digit, the rest ignored; no digit or a value
+ *                     outside a 64-bit long fails (parseChromPos, VCFX_merger.cpp:77-92).  Dropped;
+ *                     the default mode warns per line, -s is silent.
+ *   VCFXG_MG_HEADER   a '#' line of the output.  assume_sorted = 0 (mergeVCFInMemory :176-254): ALL
+ *                     '#' lines, wherever they stand, of the first file that has any.
+ *                     assume_sorted = 1 (mergeVCFStreaming :257-345): the '#' lines before the first
+ *                     line that is neither empty nor '#', of the first file that has such lines.
+ *   VCFXG_MG_DROPPED  every other '#' line
+ * The output is the header lines in input order, then the kept lines of all files.
+ * Order.  natural = 0: CHROM as unsigned bytes (a prefix before its extensions), then POS as a
+ * signed 64-bit integer.  natural = 1 (parseChromNat :43-74): the first three bytes when they are
+ * "chr" in any letter case, AS WRITTEN, are the prefix (else it is empty); the decimal digits after
+ * it are num, the rest the suffix; the order is prefix bytes, names with digits before names
+ * without, num, suffix bytes, POS.  "1" and "01" are equal keys; "chr1" and "Chr1" are not.
+ * EQUAL KEYS COME OUT IN (FILE LIST ORDER, LINE ORDER): the reference leaves them to std::sort and
+ * to its heap, so the outputs are byte-identical when no two kept lines share a key and otherwise
+ * differ only inside runs of equal keys.
+ * assume_sorted = 0, and assume_sorted = 1 when every file is non-decreasing: one stable LSD radix
+ * sort over POS, the key string's length and its 8-byte words (natural: then num and the prefix),
+ * exact for any length and any byte values (VCFXG_MG_PATH_SORT).  assume_sorted = 1 with a file
+ * out of order: the reference's heap process itself (pop the least head, the earliest file among
+ * equals; push that file's next kept line), one wave, at most VCFXG_MG_WALK_STEPS steps a launch
+ * (read by vcfxg_open; default 2^20) with the cursors in device memory (VCFXG_MG_PATH_WALK).
+ * Outside the domain: natural = 1 with a digit run of more than 18 digits (the reference then
+ * compares uninitialised values).
+ * A line whose second tab lies within its first VCFXG_MG_WINDOW bytes (or that is no longer than
+ * that) is parsed by one lane; every other line by a wave (general_records counts those).
+ * rows = written lines, data_lines = kept lines, warn_lines = BAD lines, n_lines.
+ * vcfxg_merge_counts: the lines per status (counts[VCFXG_MG_EMPTY .. VCFXG_MG_DROPPED]), the lines
+ * the wave path parsed, the path taken (VCFXG_MG_PATH_*), the header's file (n_files: none).
+ * vcfxg_merge_files: each file's first line (n_files + 1 entries, the last one n_lines) and its BAD
+ * lines (n_files entries).  vcfxg_merge_order: the input line numbers of output lines
+ * [first, first + count).  vcfxg_merge_text: output lines [first_out_line, first_out_line +
+ * *lines_taken), each with its '\n', as text bytes [0, *bytes) (vcfxg_fetch_text_range): at most
+ * VCFXG_SRT_BLOCK bytes a call (the sorter's bound and gather), one line at least; the caller goes
+ * on from there.  Every fetcher returns VCFXG_E_STATE without a vcfxg_merge on this index. */
+#define VCFXG_MG_EMPTY 0
+#define VCFXG_MG_KEPT 1
+#define VCFXG_MG_BAD 2
+#define VCFXG_MG_HEADER 3
+#define VCFXG_MG_DROPPED 4
+#define VCFXG_MG_WINDOW 64
+#define VCFXG_MG_PATH_SORT 0
+#define VCFXG_MG_PATH_WALK 1
+typedef struct {
+    const uint64_t *file_start; /* n_files + 1 offsets: where each file begins; the text's size */
+    uint32_t n_files;           /* K >= 1 */
+    int assume_sorted;          /* -s / --assume-sorted */
+    int natural;                /* -n / --natural-chr */
+} vcfxg_mg_params;
+int vcfxg_merge(vcfxg_ctx *ctx, const vcfxg_mg_params *params, vcfxg_summary *out);
+int vcfxg_merge_status(vcfxg_ctx *ctx, uint64_t first, uint64_t count, uint8_t *status);
+int vcfxg_merge_counts(const vcfxg_ctx *ctx, uint64_t counts[8]);
+int vcfxg_merge_files(vcfxg_ctx *ctx, uint64_t *first_line, uint64_t *bad);
+int vcfxg_merge_order(vcfxg_ctx *ctx, uint64_t first, uint64_t count, uint32_t *lines);
+int vcfxg_merge_text(vcfxg_ctx *ctx, uint64_t first_out_line, uint64_t *lines_taken, uint64_t *bytes);
+
 /* ---- VCFX_haplotype_phaser (LD reuse in block phasing) ------------------
  * Over the lines from data_start (the byte after the '#CHROM' line): per line status 1 variant,
  * 4 '#' line, 3 "<10 fields", 7 invalid POS, 8 no GT in FORMAT, 0 empty (mode VCFXG_MODE_FILE:

@@ -28,6 +28,7 @@
  *   vcfx_tool_fasta_converter  run/main, VCFX_fasta_converter.cpp:230-258, 533-539
  *   vcfx_tool_sorter  run/main, VCFX_sorter.cpp:676-743, 753-761
  *   vcfx_tool_diff_tool  run/main, VCFX_diff_tool.cpp:705-761, 766-783 (two files, no stdin)
+ *   vcfx_tool_merger  run/main, VCFX_merger.cpp:94-148, 355-361 (K files, no stdin)
  *   vcfx_tool_main              the `vcfx <tool> ...` dispatch (src/vcfx_wrapper/vcfx.cpp:177-187)
  * Without a usable gfx950 device a tool that reaches the record loop writes
  * "no usable MI355X" to err_fd and returns 1 (no CPU fallback).
@@ -60,6 +61,7 @@ vcfx_entry_fn vcfx_tool_multiallelic_splitter;
 vcfx_entry_fn vcfx_tool_fasta_converter;
 vcfx_entry_fn vcfx_tool_sorter;
 vcfx_entry_fn vcfx_tool_diff_tool;
+vcfx_entry_fn vcfx_tool_merger;
 /* tool = "VCFX_<name>" (a leading path is ignored); -100 for an unknown tool */
 int vcfx_tool_main(const char *tool, int argc, char **argv, int in_fd, int out_fd, int err_fd);
 /* The same invocation over ngpu device contexts in this process (one host thread per rank;

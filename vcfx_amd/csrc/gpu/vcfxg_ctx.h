@@ -174,6 +174,25 @@ struct vcfxg_ctx {
     uint64_t df_walk_steps = getenv("VCFXG_DF_WALK_STEPS")
                                  ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_DF_WALK_STEPS"), nullptr, 10), 1), 1ull << 24)
                                  : 1ull << 20;
+    // VCFX_merger: per line its file, POS and the key string's descriptor (first word, start, length;
+    // with -n the prefix word and the digit run's value), the wave pass's line list, the written
+    // flags and their scan; per file (K + 1 words each) its first byte, first line, first '#' line,
+    // first other line, BAD lines, walk cursor and end; the (key part, line) pairs of the sort and
+    // its temporary storage (mg_v0: the written lines in line order; the walk writes mg_v1); per
+    // output line its bytes, their scan and its first input byte; the walk's output count; the last
+    // call's counts, written lines and files, which of mg_v0 / mg_v1 holds the order; the offsets on
+    // the host (fetched by the first vcfxg_merge_text); steps per launch of the walk (read when the
+    // context opens; tests use 7).  The text blocks are bounded by srt_block (VCFXG_SRT_BLOCK).
+    DevBuf mg_file, mg_pos, mg_w0, mg_ks, mg_kl, mg_pn, mg_num, mg_queue, mg_written, mg_ord, mg_fmeta, mg_k0, mg_k1, mg_v0,
+        mg_v1, mg_tmp, mg_len, mg_off, mg_src, mg_state;
+    uint64_t mg_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t mg_nw = 0;
+    uint32_t mg_files = 0;
+    bool mg_done = false, mg_in_v1 = false;
+    std::vector<uint64_t> mg_off_host;
+    uint64_t mg_walk_steps = getenv("VCFXG_MG_WALK_STEPS")
+                                 ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_MG_WALK_STEPS"), nullptr, 10), 1), 1ull << 24)
+                                 : 1ull << 20;
     // VCFX_multiallelic_splitter: the table; per line of the block its tab offsets, cost and the
     // scans of nAlts and cost; each line's text offset; {lines taken, rows}; the last call's block;
     // lines and text bytes per call (read when the context opens; tests make blocks of one line)

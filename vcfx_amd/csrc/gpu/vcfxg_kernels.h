@@ -538,4 +538,53 @@ hipError_t launch_df_place(uint64_t L, const uint32_t *uflag, const uint64_t *uo
 hipError_t launch_df_sum(uint64_t L, const uint64_t *ord, const uint64_t *uord, const unsigned long long *counters,
                          uint64_t *sum, hipStream_t s);
 
+// VCFX_merger (vcfxg_mg.hip) over the L indexed lines of K files in one text (indexed from offset
+// 0); file f's bytes begin at file_start[f] (K + 1 entries, the last one the text's size).
+// launch_mg_cut: first_line[f] = the first line that starts at or after file_start[f]
+// (first_line[K] = L); first_hash / first_data = L, bad = 0.  launch_mg_key: per line its file and
+// status (kMgEmpty, kMgBad, kMgKept; every '#' line kMgHeader for now) and for a kept line POS and
+// the key string's start, length and first eight bytes big-endian (CHROM; with natural the bytes
+// after the "chr" prefix and the digit run, with pn = (prefix word << 1 | non-numeric) and num = the
+// run's value); a lane per line whose second tab lies in its first kMgWindow bytes, then a wave per
+// line that pass does not settle (queue: L entries; counters[5] counts them); first_hash[f] /
+// first_data[f] = the file's first '#' line / first line that is neither empty nor '#'.
+// launch_mg_class: counters[7] = the first file with a header candidate (K: none); the '#' lines
+// of that file (with sorted: those before its first_data) stay kMgHeader, every other one becomes
+// kMgDropped; written[li] = 1 for a header or kept line; counters[0..4] += the lines per status,
+// bad[f] += file f's kMgBad lines, counters[6] = the longest key string of a kept line.
+// launch_mg_scatter: vals[ord[line]] = line for every written line (ord: the exclusive scan of
+// written).  launch_mg_part: keys[j] = one part (kMgPart*) of the key of line vals[j], 0 for a
+// header line.  launch_mg_ordered: counters[8] = 1 when a kept line compares greater than the next
+// kept line of its file.  launch_mg_walk_init: the header block to out, state[0] = its lines, cur[f]
+// / end[f] = file f's kept lines among the written ones.  launch_mg_walk: at most `steps` steps of
+// the K-way heap process from cur and state[0] (one wave).
+enum : uint8_t { kMgEmpty = 0, kMgKept = 1, kMgBad = 2, kMgHeader = 3, kMgDropped = 4 };
+enum { kMgPartPos = 0, kMgPartLen = 1, kMgPartWord = 2, kMgPartNum = 3, kMgPartPrefix = 4 };
+constexpr int kMgWindow = 64;
+struct MgLines {
+    const char *buf;
+    const uint64_t *line_end;
+    uint64_t L;
+    uint32_t K;
+    int sorted, natural;
+    uint8_t *status;
+    uint32_t *file, *pn;
+    uint64_t *w0, *ks, *kl, *num;
+    int64_t *pos;
+    const uint64_t *file_start;
+    uint64_t *first_line, *first_hash, *first_data, *bad, *cur, *end;
+};
+hipError_t launch_mg_cut(const MgLines &M, hipStream_t s);
+hipError_t launch_mg_key(const MgLines &M, uint32_t *queue, unsigned long long *counters, hipStream_t s);
+hipError_t launch_mg_class(const MgLines &M, uint32_t *written, unsigned long long *counters, hipStream_t s);
+hipError_t launch_mg_scatter(uint64_t L, const uint32_t *written, const uint64_t *ord, uint32_t *vals, hipStream_t s);
+hipError_t launch_mg_part(const MgLines &M, uint64_t nw, int part, uint64_t w, uint32_t shift, const uint32_t *vals,
+                          uint64_t *keys, hipStream_t s);
+hipError_t launch_mg_ordered(const MgLines &M, uint64_t nw, const uint32_t *line, unsigned long long *counters,
+                             hipStream_t s);
+hipError_t launch_mg_walk_init(const MgLines &M, const uint64_t *ord, const uint32_t *line, uint32_t *out,
+                               const unsigned long long *counters, uint64_t *state, hipStream_t s);
+hipError_t launch_mg_walk(const MgLines &M, const uint32_t *line, uint32_t *out, uint64_t steps, uint64_t *state,
+                          hipStream_t s);
+
 }  // namespace vcfxg

@@ -52,6 +52,11 @@ class DfParams(ctypes.Structure):
                 ("hash_bits", ctypes.c_uint32)]
 
 
+class MgParams(ctypes.Structure):
+    _fields_ = [("file_start", ctypes.c_void_p), ("n_files", ctypes.c_uint32), ("assume_sorted", ctypes.c_int),
+                ("natural", ctypes.c_int)]
+
+
 class CcParams(ctypes.Structure):
     _fields_ = [("n_samples", ctypes.c_uint32), ("mult", ctypes.c_void_p), ("n_mult", ctypes.c_uint64),
                 ("threads", ctypes.c_uint64)]
@@ -126,6 +131,12 @@ SIGNATURES = {
     "vcfxg_diff_status": (_I, [_VP, _U64, _U64, _VP]),
     "vcfxg_diff_counts": (_I, [_VP, _VP]),
     "vcfxg_diff_text": (_I, [_VP, _I, _U64, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "vcfxg_merge": (_I, [_VP, _VP, ctypes.POINTER(Summary)]),
+    "vcfxg_merge_status": (_I, [_VP, _U64, _U64, _VP]),
+    "vcfxg_merge_counts": (_I, [_VP, _VP]),
+    "vcfxg_merge_files": (_I, [_VP, _VP, _VP]),
+    "vcfxg_merge_order": (_I, [_VP, _U64, _U64, _VP]),
+    "vcfxg_merge_text": (_I, [_VP, _U64, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "vcfxg_multiallelic_split": (_I, [_VP, _U64, _U64, _VP, ctypes.POINTER(Summary)]),
     "vcfxg_ms_line_ranges": (_I, [_VP, _U64, _U64, _VP]),
     "vcfxg_fasta_scan": (_I, [_VP, _U64, _U64, _I, ctypes.c_uint32, ctypes.POINTER(Summary)]),
@@ -512,6 +523,48 @@ class Engine:
         out, j = [], 0
         while j < cnt[int(side)]:
             k, text = self.diff_text(side, j)
+            out.append(text)
+            j += k
+        return b"".join(out)
+
+    def merge(self, file_starts, assume_sorted=False, natural=False):
+        """VCFX_merger over the indexed lines of K files loaded as one text (every file in list order,
+        a newline after one that lacks its last; index(0) first; vcfxg_merge): file_starts = the K + 1
+        bytes where the files begin, the last one the text's size.  Returns (summary, statuses uint8
+        per line: VCFXG_MG_*, counts: the lines per status, wave-path lines, the path taken, the
+        header's file, order: the input line number of every output line)."""
+        import numpy as np
+        fs = np.ascontiguousarray(file_starts, np.uint64)
+        p = MgParams(fs.ctypes.data, len(fs) - 1, int(bool(assume_sorted)), int(bool(natural)))
+        s = Summary()
+        self._chk(self.L.vcfxg_merge(self.h, ctypes.byref(p), ctypes.byref(s)), "merge")
+        st = np.zeros(max(int(s.n_lines), 1), np.uint8)
+        self._chk(self.L.vcfxg_merge_status(self.h, 0, s.n_lines, st.ctypes.data), "merge_status")
+        cnt = np.zeros(8, np.uint64)
+        self._chk(self.L.vcfxg_merge_counts(self.h, cnt.ctypes.data), "merge_counts")
+        order = np.zeros(max(int(s.rows), 1), np.uint32)
+        self._chk(self.L.vcfxg_merge_order(self.h, 0, s.rows, order.ctypes.data), "merge_order")
+        return s, st[:s.n_lines], tuple(int(x) for x in cnt), order[:s.rows]
+
+    def merge_files(self, n_files):
+        """each file's first line (n_files + 1 entries) and its BAD lines of the last merge()"""
+        import numpy as np
+        first, bad = np.zeros(n_files + 1, np.uint64), np.zeros(max(n_files, 1), np.uint64)
+        self._chk(self.L.vcfxg_merge_files(self.h, first.ctypes.data, bad.ctypes.data), "merge_files")
+        return [int(x) for x in first], [int(x) for x in bad[:n_files]]
+
+    def merge_text(self, first):
+        """output lines [first, first + lines) of the last merge() gathered on the device, one block
+        of at most VCFXG_SRT_BLOCK bytes (vcfxg_merge_text): (lines taken, their bytes)"""
+        k, n = ctypes.c_uint64(), ctypes.c_uint64()
+        self._chk(self.L.vcfxg_merge_text(self.h, int(first), ctypes.byref(k), ctypes.byref(n)), "merge_text")
+        return k.value, self.text_range(0, n.value)
+
+    def merged_text(self, rows):
+        """the whole output of the last merge() (rows = its summary's rows), block after block"""
+        out, j = [], 0
+        while j < rows:
+            k, text = self.merge_text(j)
             out.append(text)
             j += k
         return b"".join(out)
