@@ -117,7 +117,8 @@ sanitize: $(SAN)/host_san_asan $(SAN)/host_san_tsan $(SAN)/core_api_asan $(SAN)/
     $(if $(wildcard tests/host_fa_test.cpp),$(SAN)/host_fa_asan) \
     $(if $(wildcard tests/host_df_test.cpp),$(SAN)/host_df_asan) \
     $(if $(wildcard tests/host_mg_test.cpp),$(SAN)/host_mg_asan) \
-    $(if $(wildcard tests/decimal_bounds_test.cpp),$(SAN)/decimal_bounds_asan)
+    $(if $(wildcard tests/decimal_bounds_test.cpp),$(SAN)/decimal_bounds_asan) \
+    $(if $(wildcard tests/walk_layout_test.cpp),$(SAN)/walk_layout_asan)
 $(SAN)/host_san_asan: $(SAN_HOST_SRC) $(wildcard $(HOST_SRC)/*.h) $(B)/libvcfx_gpu.so
 	@mkdir -p $(dir $@)
 	$(CXX) $(SANFLAGS) -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $(SAN_HOST_SRC) \
@@ -178,4 +179,9 @@ $(SAN)/decimal_bounds_asan: tests/decimal_bounds_test.cpp $(GPU_SRC)/vcfxg_decim
 	@mkdir -p $(dir $@)
 	$(CXX) $(SANFLAGS) -I$(GPU_SRC) -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 	    -o $@ tests/decimal_bounds_test.cpp $(GPU_SRC)/vcfxg_decimal.cpp
+# the record walk's chunk layout (vcfxg_walk_layout.h: plain C++, shared by the kernel and the plan)
+# under ASan + UBSan: cases in, every walker's bytes out (tests/test_walk_layout_cpu.py checks the tiling)
+$(SAN)/walk_layout_asan: tests/walk_layout_test.cpp $(GPU_SRC)/vcfxg_walk_layout.h
+	@mkdir -p $(dir $@)
+	$(CXX) $(SANFLAGS) -I$(GPU_SRC) -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
 .PHONY: sanitize

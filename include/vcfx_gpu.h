@@ -899,6 +899,14 @@ const char *vcfxg_last_schedule(const vcfxg_ctx *ctx);
  * longer than that continues rolling; chosen from the input's sample count, or forced by
  * VCFXG_AF_DEPTH (read when the context opens).  A diagnostic for tests */
 int vcfxg_last_af_depth(const vcfxg_ctx *ctx, int *rolling);
+/* the chunk layout of the last allele-frequency walk over GT-only records.  Returns its kind (0: no
+ * such walk yet, 1 uniform, 2 fit, 3 taper, 4 split) and fills out[0..7]: a walker's bytes in the
+ * full-size rounds and in the short ones, the first short dispatch round (-1: none), the blocks
+ * launched, the walkers that own bytes, the resident walkers the layout was planned for (0: not
+ * asked), and the taper's or split's divisor and second number.  Chosen by the plan from the region's
+ * size and the resident walkers, or forced by VCFXG_WALK_LAYOUT = uniform | fit | taper:<div>:<g> |
+ * split:<div>:<K1> (read when the context opens).  A diagnostic for tests */
+int vcfxg_last_walk_layout(const vcfxg_ctx *ctx, int64_t out[8]);
 
 /* device-formatted output text (without the column header line) */
 int vcfxg_fetch_text(vcfxg_ctx *ctx, char *host, size_t cap);

@@ -1,6 +1,8 @@
 // vcfxg_af_walk.hip -- VCFX_allele_freq_calc's record pass without a separate line index.
 //
-// The data region is cut into C-byte chunks, one wave ("walker") each.  A walker's lines are
+// The data region is cut into chunks, one wave ("walker") each: C bytes, or, for the AF GT-only
+// walk, the plan's two-segment layout (vcfxg_walk_layout.h: full-size walkers in the first dispatch
+// rounds, shorter ones last).  A walker's lines are
 // those starting in [b(chunk start), b(chunk end)), b(x) the byte after the last '\n' before x
 // (vcfxg_walk.h walker_lines: two short backward scans; the line across a chunk boundary goes
 // to the walker after it, which reads it first).  It walks its lines one after the other:
@@ -100,47 +102,49 @@ __global__ __launch_bounds__(256) void k_walk_compact(int64_t n_walkers, uint64_
 
 int64_t af_walkers(int64_t lo, int64_t hi, int64_t chunk) { return hi > lo ? (hi - lo + chunk - 1) / chunk : 0; }
 
-hipError_t launch_af_walk(const char *buf, int64_t lo, int64_t hi, int64_t chunk, int mode, int64_t span0,
+int af_walk_waves_per_block() { return kWalkWaves; }
+
+// the AF GT-only walk's kernel for (depth, roll); null if not compiled
+typedef decltype(&k_af_walk<AfOp>) AfWalkKernel;
+static AfWalkKernel af_gt_only_kernel(int depth, bool roll) {
+    if (!roll) return depth == kWalkUnroll ? k_af_walk<AfOp> : nullptr;
+    return depth == 6 ? k_af_walk<AfOp, false, 6, true>
+         : depth == 8 ? k_af_walk<AfOp, false, 8, true>
+         : depth == 10 ? k_af_walk<AfOp, false, 10, true>
+         : depth == 12 ? k_af_walk<AfOp, false, 12, true>
+                       : nullptr;
+}
+
+int af_walk_resident_blocks(int depth, bool roll) {
+    const AfWalkKernel k = af_gt_only_kernel(depth, roll);
+    int blocks = 0;
+    if (!k || hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k, kWalkThreads, 0) != hipSuccess) return 0;
+    return blocks;
+}
+
+hipError_t launch_af_walk(const char *buf, int64_t lo, int64_t hi, const WalkLayout &lay, int mode, int64_t span0,
                           uint64_t cap_w, uint64_t *le_b, int32_t *alt_b, int32_t *tot_b, uint32_t *rowpre_b,
                           uint8_t *status_b, void *meta_b, uint64_t *wcount, uint32_t *wgt, unsigned *overflow,
                           hipStream_t s, int32_t *hwe_aux_b, const WalkTail *tail, bool dose, bool gt_first_walk,
                           bool dose_head, int depth, bool roll) {
     const WalkTail t = tail ? *tail : WalkTail{};
-    const int64_t nw = af_walkers(lo, hi, chunk);
-    if (!nw) return hipErrorInvalidValue;
+    if (!lay.nw || !lay.grid) return hipErrorInvalidValue;
     // the compiled sweeps: the batches of kWalkUnroll wave-steps for every walk; for the AF GT-only
     // walk also the rolling sweeps of af_depth_compiled
     const bool af_gt_only = !gt_first_walk && !dose && !hwe_aux_b;
     if (roll ? !(af_gt_only && af_depth_compiled(depth)) : depth != kWalkUnroll) return hipErrorInvalidValue;
-    const unsigned grid = (unsigned)((nw + kWalkWaves - 1) / kWalkWaves);
-    if (gt_first_walk)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_af_walk<AfOp, true>), dim3(grid), dim3(kWalkThreads), 0, s, buf, lo, hi,
-                           chunk, nw, mode, span0, cap_w, le_b, alt_b, tot_b, nullptr, rowpre_b, status_b,
-                           static_cast<LineMeta *>(meta_b), wcount, wgt, overflow, t);
-    else if (dose && dose_head)
-        hipLaunchKernelGGL(k_af_walk<DoseHeadOp>, dim3(grid), dim3(kWalkThreads), 0, s, buf, lo, hi, chunk, nw, mode,
-                           span0, cap_w, le_b, alt_b, tot_b, nullptr, rowpre_b, status_b, static_cast<LineMeta *>(meta_b),
-                           wcount, wgt, overflow, t);
-    else if (dose)
-        hipLaunchKernelGGL(k_af_walk<DoseWalkOp>, dim3(grid), dim3(kWalkThreads), 0, s, buf, lo, hi, chunk, nw, mode,
-                           span0, cap_w, le_b, alt_b, tot_b, nullptr, rowpre_b, status_b, static_cast<LineMeta *>(meta_b),
-                           wcount, wgt, overflow, t);
-    else if (hwe_aux_b)
-        hipLaunchKernelGGL(k_af_walk<HweOp>, dim3(grid), dim3(kWalkThreads), 0, s, buf, lo, hi, chunk, nw, mode, span0,
-                           cap_w, le_b, alt_b, tot_b, hwe_aux_b, rowpre_b, status_b, static_cast<LineMeta *>(meta_b),
-                           wcount, wgt, overflow, t);
-    else {
-        auto go = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kWalkThreads), 0, s, buf, lo, hi, chunk, nw, mode, span0, cap_w,
-                               le_b, alt_b, tot_b, nullptr, rowpre_b, status_b, static_cast<LineMeta *>(meta_b), wcount,
-                               wgt, overflow, t);
-        };
-        if (!roll) go(k_af_walk<AfOp>);  // (depth kWalkUnroll: checked above)
-        else if (depth == 6) go(k_af_walk<AfOp, false, 6, true>);
-        else if (depth == 8) go(k_af_walk<AfOp, false, 8, true>);
-        else if (depth == 10) go(k_af_walk<AfOp, false, 10, true>);
-        else go(k_af_walk<AfOp, false, 12, true>);
-    }
+    // every walk but the AF GT-only one keeps the uniform layout
+    if (!af_gt_only && lay.K1 != kWalkAllRounds) return hipErrorInvalidValue;
+    auto go = [&](auto kernel, int32_t *aux_b) {
+        hipLaunchKernelGGL(kernel, dim3(lay.grid), dim3(kWalkThreads), 0, s, buf, lo, hi, lay, mode, span0, cap_w, le_b,
+                           alt_b, tot_b, aux_b, rowpre_b, status_b, static_cast<LineMeta *>(meta_b), wcount, wgt,
+                           overflow, t);
+    };
+    if (gt_first_walk) go(k_af_walk<AfOp, true>, nullptr);
+    else if (dose && dose_head) go(k_af_walk<DoseHeadOp>, nullptr);
+    else if (dose) go(k_af_walk<DoseWalkOp>, nullptr);
+    else if (hwe_aux_b) go(k_af_walk<HweOp>, hwe_aux_b);
+    else go(af_gt_only_kernel(depth, roll), nullptr);  // (compiled: checked above)
     return hipGetLastError();
 }
 

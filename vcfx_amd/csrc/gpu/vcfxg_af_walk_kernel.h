@@ -143,8 +143,7 @@ __attribute__((amdgpu_waves_per_eu(1, VCFXG_WALK_MAXW)))
 #else
 __attribute__((amdgpu_waves_per_eu(af_walk_waves(kGF, kDepth))))
 #endif
-void k_af_walk(const char *__restrict__ buf, int64_t lo, int64_t hi, int64_t chunk, int64_t n_walkers, int mode,
-               int64_t span0, uint64_t cap_w, uint64_t *__restrict__ le_o, int32_t *__restrict__ alt_o,
+void k_af_walk(const char *__restrict__ buf, int64_t lo, int64_t hi, WalkLayout lay, int mode, int64_t span0, uint64_t cap_w, uint64_t *__restrict__ le_o, int32_t *__restrict__ alt_o,
                int32_t *__restrict__ tot_o, int32_t *__restrict__ aux_o, uint32_t *__restrict__ rowpre_o,
                uint8_t *__restrict__ status_o, LineMeta *__restrict__ meta_o, uint64_t *__restrict__ wcount,
                uint32_t *__restrict__ wgt, unsigned *overflow, WalkTail tail) {
@@ -162,13 +161,14 @@ void k_af_walk(const char *__restrict__ buf, int64_t lo, int64_t hi, int64_t chu
     constexpr uint32_t kStgCap = kStageLds ? 2048u : 16u;
     __shared__ __attribute__((aligned(16))) char stg[kStageLds ? kWalkWaves : 1][kStgCap];
     const int wv = threadIdx.x / kWave;
-    const int64_t wk = uniform64((int64_t)walk_block() * kWalkWaves + wv);
-    if (wk >= n_walkers) return;
+    // this walker's bytes [cs, ce) of the layout (vcfxg_walk_layout.h; all wave-uniform)
+    int64_t cs, ce, wsize;
+    const int64_t wk = walk_range(lay, blockIdx.x, gridDim.x, __builtin_amdgcn_readfirstlane(wv), kWalkWaves, hi,
+                                  VCFXG_WALK_XCD != 0, cs, ce, wsize);
+    if (wk >= lay.nw) return;
     const int strip_cr = mode == 0 ? 1 : 0;
-    const int64_t cs = lo + wk * chunk;
-    const int64_t ce = std::min<int64_t>(cs + chunk, hi);
     int64_t L, ce2;  // this walker's lines start in [L, ce2)
-    walker_lines(buf, lo, hi, cs, ce, L, ce2, chunk);
+    walker_lines(buf, lo, hi, cs, ce, L, ce2, wsize);
     const int64_t L0 = L;
     uint64_t wtext = 0;  // region tail (tail.wtext): bytes of this walker's GT-line rows
     int64_t span = span0;  // predicted '\n' distance from the sample start

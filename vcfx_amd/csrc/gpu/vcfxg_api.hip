@@ -605,6 +605,19 @@ int vcfxg_last_af_depth(const vcfxg_ctx *c, int *rolling) {
     if (rolling) *rolling = c && c->last_af_roll ? 1 : 0;
     return c ? c->last_af_depth : 0;
 }
+int vcfxg_last_walk_layout(const vcfxg_ctx *c, int64_t out[8]) {
+    if (!c || !out) return 0;
+    const vcfxg::WalkLayout &l = c->last_walk_layout;
+    out[0] = l.C;
+    out[1] = l.Cs;
+    out[2] = l.K1 == vcfxg::kWalkAllRounds ? -1 : (int64_t)l.K1;
+    out[3] = l.grid;
+    out[4] = l.nw;
+    out[5] = c->last_walk_resident;
+    out[6] = c->last_walk_layout_kind.div;
+    out[7] = c->last_walk_layout_kind.g;
+    return c->last_walk_layout_kind.kind;
+}
 uint64_t vcfxg_bgzf_handed_over(const vcfxg_ctx *c) { return c ? c->bgz_handed : 0; }
 
 int vcfxg_fetch_text_range(vcfxg_ctx *c, uint64_t offset, size_t n, void *host) {

@@ -159,8 +159,8 @@ static int af_region_async(vcfxg_ctx *c, size_t data_start, int mode, vcfxg_summ
 static int af_region_walk(vcfxg_ctx *c, size_t data_start, int mode, vcfxg_summary *out, bool gf = false) {
     if (c) c->dense_pending = false;  // a new index / regions replace the pending ones
     HIPCHK(c, hipSetDevice(c->device));
-    const WalkPlan pl = walk_plan(c, data_start);
-    const int64_t lo = pl.lo, hi = pl.hi, C = pl.C, nw = pl.nw;
+    const WalkPlan pl = walk_plan(c, data_start, 0, !gf);  // (the GT-only walk: the plan's layout)
+    const int64_t lo = pl.lo, hi = pl.hi, nw = pl.nw;
     if (!nw) {
         int r = vcfxg_index(c, data_start, nullptr);
         return r ? r : vcfxg_allele_freq(c, mode, out);
@@ -208,9 +208,12 @@ static int af_region_walk(vcfxg_ctx *c, size_t data_start, int mode, vcfxg_summa
     // (the GT-first walk has one sweep of its own)
     const int depth = gf ? vcfxg::kAfDepthDefault : pl.af_depth;
     const bool roll = !gf && pl.af_roll;
-    if (!gf) c->last_af_depth = depth, c->last_af_roll = roll;
+    if (!gf) {
+        c->last_af_depth = depth, c->last_af_roll = roll;
+        c->last_walk_layout = pl.lay, c->last_walk_layout_kind = pl.lay_kind, c->last_walk_resident = pl.resident;
+    }
     prof_begin(c, "af_walk");
-    HIPCHK(c, vcfxg::launch_af_walk(buf, lo, hi, C, mode, c->hint_span, cap_w, P<uint64_t>(c->wk_le),
+    HIPCHK(c, vcfxg::launch_af_walk(buf, lo, hi, pl.lay, mode, c->hint_span, cap_w, P<uint64_t>(c->wk_le),
                                     P<int32_t>(c->wk_alt), P<int32_t>(c->wk_tot), P<uint32_t>(c->wk_rowpre),
                                     P<uint8_t>(c->wk_status), c->wk_meta.p, P<uint64_t>(c->wk_count),
                                     P<uint32_t>(c->wk_gt), ovf, c->stream, nullptr, &tail, false, gf, false, depth,

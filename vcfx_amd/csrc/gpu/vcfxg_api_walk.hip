@@ -14,12 +14,61 @@
 
 namespace vcfxg {
 
-WalkPlan walk_plan(const vcfxg_ctx *c, size_t data_start, int64_t chunk) {
+// walkers of the AF GT-only walk's (depth, roll) kernel resident on the device at a time: the
+// blocks a CU holds x its CUs x the walkers of a block, queried once per context and instantiation
+static int64_t walk_resident(const vcfxg_ctx *c, int depth, bool roll) {
+    if (c->walk_resident_knob > 0) return c->walk_resident_knob;
+    if (depth < 0 || depth > kAfDepthMax) return 0;
+    int64_t &S = c->walk_resident[roll ? 1 : 0][depth];
+    if (!S) {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess) cus = 0;
+        S = (int64_t)af_walk_resident_blocks(depth, roll) * cus * af_walk_waves_per_block();
+        if (S <= 0) S = -1;  // (asked, unknown: the uniform layout)
+    }
+    return S > 0 ? S : 0;
+}
+
+// The AF GT-only walk's default layout: a main chunk of 256 KiB (where VCFXG_WALK_CHUNK does not
+// set one), fitted to whole generations of the resident walkers, the last generation's bytes in
+// half-size walkers -- where the region is at least one generation of that main chunk; a smaller
+// region keeps the uniform walk_chunk.  A function of the region and the resident walkers alone.
+// Measured on the 427,409 x 2,504 shard (profiles/af_layout_sweep.json, in one context per process):
+// 3-6 % under the uniform 128 KiB chunks in every process; fit alone at 128 KiB: nothing.
+static constexpr int64_t kAfMainChunk = 256 << 10;
+static constexpr WalkLayoutKnob kDefaultLayout = {kLayoutTaper, 2, 1};
+
+WalkPlan walk_plan(const vcfxg_ctx *c, size_t data_start, int64_t chunk, bool af_gt_only) {
     WalkPlan p;
     p.lo = (int64_t)data_start;
     p.hi = (int64_t)c->n;
-    p.C = chunk ? chunk : c->walk_chunk;
-    p.nw = af_walkers(p.lo, p.hi, p.C);
+    int64_t C0 = chunk ? chunk : c->walk_chunk;
+    int knob = c->af_depth_knob;
+    WalkLayoutKnob lk = c->walk_layout_knob;
+#if VCFXG_AF_DEPTH_LIVE
+    knob = getenv("VCFXG_AF_DEPTH") ? atoi(getenv("VCFXG_AF_DEPTH")) : 0;
+    lk = parse_walk_layout(getenv("VCFXG_WALK_LAYOUT"));
+    if (!chunk && getenv("VCFXG_WALK_CHUNK"))
+        C0 = std::min<int64_t>(std::max<int64_t>(atol(getenv("VCFXG_WALK_CHUNK")), 4096), 8 << 20);
+#endif
+    af_sweep_plan(c->hint_span, knob, p.af_depth, p.af_roll);
+    if (!af_gt_only) lk = WalkLayoutKnob{kLayoutUniform, 1, 0};
+    if (lk.kind == kLayoutDefault) {
+        const int64_t main = chunk || getenv("VCFXG_WALK_CHUNK") ? C0 : std::max(C0, kAfMainChunk);
+        const int64_t S = walk_resident(c, p.af_depth, p.af_roll);
+        if (S > 0 && (p.hi - p.lo + main - 1) / main >= S) {
+            lk = kDefaultLayout;
+            C0 = main;
+        } else {
+            lk = WalkLayoutKnob{kLayoutUniform, 1, 0};
+        }
+    }
+    p.resident = lk.kind == kLayoutFit || lk.kind == kLayoutTaper ? walk_resident(c, p.af_depth, p.af_roll) : 0;
+    p.lay_kind = lk;
+    p.lay = walk_layout_plan(p.lo, p.hi, C0, p.resident, lk, af_walk_waves_per_block(), VCFXG_WALK_XCD != 0,
+                             &p.lay_kind.kind);
+    p.C = p.lay.C;
+    p.nw = p.lay.nw;
     // a walker's line slots: twice the lines its chunk holds at the hinted mean length
     p.cap_w = (uint64_t)(2 * p.C / std::max<int64_t>(c->hint_line, 64)) + 16;
     p.cap = (uint64_t)p.nw * p.cap_w;
@@ -29,11 +78,6 @@ WalkPlan walk_plan(const vcfxg_ctx *c, size_t data_start, int64_t chunk) {
     // slots.  (The HWE walk launches k_af_walk too but never reads the packed count -- it zeroes
     // `counters` after the compaction -- and the fq, md and ib walks pack none: no check there.)
     p.fits_gt16 = p.cap_w <= 0xFFFF;
-    int knob = c->af_depth_knob;
-#if VCFXG_AF_DEPTH_LIVE
-    knob = getenv("VCFXG_AF_DEPTH") ? atoi(getenv("VCFXG_AF_DEPTH")) : 0;
-#endif
-    af_sweep_plan(c->hint_span, knob, p.af_depth, p.af_roll);
     return p;
 }
 
@@ -143,12 +187,12 @@ int af_walk_to_dense(vcfxg_ctx *c, const WalkPlan &p, int mode, const char *prof
     HIPCHK(c, hipMemsetAsync(P<uint64_t>(c->wk_count) + p.nw, 0, 8, c->stream));
     prof_begin(c, prof_name);
     if (cc)
-        HIPCHK(c, launch_cc_walk(P<char>(c->input), p.lo, p.hi, p.C, mode, c->hint_span, p.cap_w, P<uint64_t>(c->wk_le),
+        HIPCHK(c, launch_cc_walk(P<char>(c->input), p.lo, p.hi, p.lay, mode, c->hint_span, p.cap_w, P<uint64_t>(c->wk_le),
                                  P<int32_t>(c->wk_alt), P<int32_t>(c->wk_tot), P<uint32_t>(c->wk_rowpre),
                                  P<uint8_t>(c->wk_status), c->wk_meta.p, P<uint64_t>(c->wk_count), P<uint32_t>(c->wk_gt),
                                  P<unsigned>(c->wk_small), c->stream));
     else
-        HIPCHK(c, launch_af_walk(P<char>(c->input), p.lo, p.hi, p.C, mode, c->hint_span, p.cap_w, P<uint64_t>(c->wk_le),
+        HIPCHK(c, launch_af_walk(P<char>(c->input), p.lo, p.hi, p.lay, mode, c->hint_span, p.cap_w, P<uint64_t>(c->wk_le),
                              P<int32_t>(c->wk_alt), P<int32_t>(c->wk_tot), P<uint32_t>(c->wk_rowpre),
                              P<uint8_t>(c->wk_status), c->wk_meta.p, P<uint64_t>(c->wk_count), P<uint32_t>(c->wk_gt),
                              P<unsigned>(c->wk_small), c->stream, aux ? P<int32_t>(c->wk_aux) : nullptr, nullptr, dose,

@@ -330,15 +330,14 @@ static unsigned cc_grid(uint64_t n, uint64_t per, unsigned cap) {
     return (unsigned)(g > cap ? cap : g);
 }
 
-hipError_t launch_cc_walk(const char *buf, int64_t lo, int64_t hi, int64_t chunk, int mode, int64_t span0,
+hipError_t launch_cc_walk(const char *buf, int64_t lo, int64_t hi, const WalkLayout &lay, int mode, int64_t span0,
                           uint64_t cap_w, uint64_t *le_b, int32_t *alt_b, int32_t *tot_b, uint32_t *rowpre_b,
                           uint8_t *status_b, void *meta_b, uint64_t *wcount, uint32_t *wgt, unsigned *overflow,
                           hipStream_t s) {
-    const int64_t nw = af_walkers(lo, hi, chunk);
-    if (!nw) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_af_walk<CcOp>, dim3((unsigned)((nw + kWalkWaves - 1) / kWalkWaves)), dim3(kWalkThreads), 0, s,
-                       buf, lo, hi, chunk, nw, mode, span0, cap_w, le_b, alt_b, tot_b, nullptr, rowpre_b, status_b,
-                       static_cast<LineMeta *>(meta_b), wcount, wgt, overflow, WalkTail{});
+    if (!lay.nw || !lay.grid || lay.K1 != kWalkAllRounds) return hipErrorInvalidValue;  // (the uniform layout)
+    hipLaunchKernelGGL(k_af_walk<CcOp>, dim3(lay.grid), dim3(kWalkThreads), 0, s, buf, lo, hi, lay, mode, span0, cap_w,
+                       le_b, alt_b, tot_b, nullptr, rowpre_b, status_b, static_cast<LineMeta *>(meta_b), wcount, wgt,
+                       overflow, WalkTail{});
     return hipGetLastError();
 }
 

@@ -259,6 +259,18 @@ struct vcfxg_ctx {
     int af_depth_knob = getenv("VCFXG_AF_DEPTH") ? atoi(getenv("VCFXG_AF_DEPTH")) : 0;
     int last_af_depth = 0;        // the depth / rolling of the last AF GT-only walk launched
     bool last_af_roll = false;    // (vcfxg_last_af_depth; 0: none yet)
+    // the AF GT-only walk's chunk layout (walk_plan): VCFXG_WALK_LAYOUT = uniform | fit |
+    // taper:<div>:<g> | split:<div>:<K1> (a test's explicit first short round), read when the context
+    // opens; unset or anything else: the plan's default
+    vcfxg::WalkLayoutKnob walk_layout_knob = vcfxg::parse_walk_layout(getenv("VCFXG_WALK_LAYOUT"));
+    // the walkers resident at a time, per compiled (depth, roll) of the AF GT-only walk (queried once
+    // each; 0: not yet); VCFXG_WALK_RESIDENT overrides the query (tests: a small device's layouts on
+    // small inputs)
+    mutable int64_t walk_resident[2][vcfxg::kAfDepthMax + 1] = {};
+    int64_t walk_resident_knob = getenv("VCFXG_WALK_RESIDENT") ? atoll(getenv("VCFXG_WALK_RESIDENT")) : 0;
+    vcfxg::WalkLayoutKnob last_walk_layout_kind;  // of the last AF GT-only walk launched
+    vcfxg::WalkLayout last_walk_layout = {};      // (vcfxg_last_walk_layout)
+    int64_t last_walk_resident = 0;
     // record_filter / genotype_query region schedule: 0 = the walk (vcfxg_fq_walk.hip) when
     // the first records average >= 512 B, 1 = the walk always, -1 = index + per-tool kernels
     int fq_path = getenv("VCFXG_FQ_WALK") ? atoi(getenv("VCFXG_FQ_WALK")) : 0;
@@ -344,14 +356,20 @@ int ensure_sum_host(vcfxg_ctx *c);
 // af_depth / af_roll: the AF GT-only walk's sweep (launch_af_walk depth / roll), from the hinted
 // sample span: a rolling non-temporal sweep of the depth that the A/B of that record size showed
 // faster, else the batches of kAfDepthDefault; VCFXG_AF_DEPTH forces a compiled depth
+// lay: the walkers' bytes (vcfxg_walk_layout.h): uniform chunks of C for every walk but the AF
+// GT-only one (af_gt_only), whose layout the plan chooses from the region's size and the walkers
+// resident at a time (VCFXG_WALK_LAYOUT forces one); C is then the larger chunk, nw = lay.nw
 struct WalkPlan {
     int64_t lo, hi, C, nw;
     uint64_t cap_w, cap;
     bool fits_gt16;
     int af_depth;
     bool af_roll;
+    WalkLayout lay;
+    WalkLayoutKnob lay_kind;  // what the layout came to (kind; taper / split: div and g / K1 as asked)
+    int64_t resident;         // the resident walkers it was planned for (0: not asked)
 };
-WalkPlan walk_plan(const vcfxg_ctx *c, size_t data_start, int64_t chunk = 0);
+WalkPlan walk_plan(const vcfxg_ctx *c, size_t data_start, int64_t chunk = 0, bool af_gt_only = false);
 void af_sweep_plan(int64_t span, int knob, int &depth, bool &roll);
 // the input-derived half of "does this call walk": long records (of FORMAT exactly "GT" where the
 // walk's kernel needs that) and no walk overflow on this input yet

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vcfxg_walk_layout.h"
+
 namespace vcfxg {
 
 // per-line head summary shared by the AF / GQ head passes (k_line_meta, k_af_combine)
@@ -89,6 +91,10 @@ int64_t idx_wchunk_bytes();
 // walks its lines (predicted fixed-stride ends validated by the sweep); per-walker regions
 // of cap_w lines, then k_walk_compact (offs = exclusive scan of wcount)
 int64_t af_walkers(int64_t lo, int64_t hi, int64_t chunk);
+// walkers (waves) per block of k_af_walk, and the blocks of one instantiation of it that a CU holds
+// at a time (hipOccupancyMaxActiveBlocksPerMultiprocessor on the current device; 0 on error)
+int af_walk_waves_per_block();
+int af_walk_resident_blocks(int depth, bool roll);
 // the AF walk's region tail (all null: the walk only fills its regions): per walker its row
 // bytes (GT lines) and first line start, and the list of region slots left to the exact
 // per-line path (kMetaFull lines, GT lines off the fixed-stride sweep)
@@ -112,7 +118,9 @@ struct WalkTail {
 constexpr int kAfDepthDefault = 6, kAfDepthMax = 12;
 constexpr int kAfWaveStep = 1024;  // bytes of a wave-step (vcfxg_device.h kWaveStep, for the host's plan)
 constexpr bool af_depth_compiled(int d) { return d == 6 || d == 8 || d == 10 || d == 12; }
-hipError_t launch_af_walk(const char *buf, int64_t lo, int64_t hi, int64_t chunk, int mode, int64_t span0,
+// lay: the walkers' bytes (vcfxg_walk_layout.h; walk_layout_make over [lo, hi) with kWalkWaves
+// walkers a block): its grid is launched, its first nw walkers write their regions
+hipError_t launch_af_walk(const char *buf, int64_t lo, int64_t hi, const WalkLayout &lay, int mode, int64_t span0,
                           uint64_t cap_w, uint64_t *le_b, int32_t *alt_b, int32_t *tot_b, uint32_t *rowpre_b,
                           uint8_t *status_b, void *meta_b, uint64_t *wcount, uint32_t *wgt, unsigned *overflow,
                           hipStream_t s, int32_t *hwe_aux_b = nullptr, const WalkTail *tail = nullptr,
@@ -120,7 +128,7 @@ hipError_t launch_af_walk(const char *buf, int64_t lo, int64_t hi, int64_t chunk
                           int depth = kAfDepthDefault, bool roll = false);
 // the same walk with the concordance reducer (vcfxg_cc.hip: k_af_walk<CcOp>): valid samples and
 // distinct keys of every fixed-stride record as alt_b / tot_b
-hipError_t launch_cc_walk(const char *buf, int64_t lo, int64_t hi, int64_t chunk, int mode, int64_t span0,
+hipError_t launch_cc_walk(const char *buf, int64_t lo, int64_t hi, const WalkLayout &lay, int mode, int64_t span0,
                           uint64_t cap_w, uint64_t *le_b, int32_t *alt_b, int32_t *tot_b, uint32_t *rowpre_b,
                           uint8_t *status_b, void *meta_b, uint64_t *wcount, uint32_t *wgt, unsigned *overflow,
                           hipStream_t s);

@@ -152,6 +152,7 @@ SIGNATURES = {
     "vcfxg_comm_rccl_stats": (_I, [_VP, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "vcfxg_last_schedule": (_P, [_VP]),
     "vcfxg_last_af_depth": (_I, [_VP, ctypes.POINTER(_I)]),
+    "vcfxg_last_walk_layout": (_I, [_VP, ctypes.POINTER(ctypes.c_int64)]),
     "vcfxg_bgzf_handed_over": (_U64, [_VP]),
     "vcfxg_count_byte": (_I, [_VP, _U64, _I, ctypes.POINTER(_U64)]),
     "vcfxg_haplotype_phaser": (_I, [_VP, _S, _I, ctypes.c_double, ctypes.c_uint32, ctypes.POINTER(Summary)]),
@@ -321,6 +322,16 @@ class Engine:
         r = ctypes.c_int()
         d = self.L.vcfxg_last_af_depth(self.h, ctypes.byref(r))
         return d, bool(r.value)
+
+    def last_walk_layout(self):
+        """The chunk layout of the last AF walk over GT-only records: a dict with its kind ("uniform", "fit",
+        "taper", "split"; None: no such walk yet), C, Cs, K1 (-1: no short round), grid, walkers, resident,
+        div and g."""
+        out = (ctypes.c_int64 * 8)()
+        kind = self.L.vcfxg_last_walk_layout(self.h, out)
+        d = dict(zip(("C", "Cs", "K1", "grid", "walkers", "resident", "div", "g"), [int(v) for v in out]))
+        d["kind"] = (None, "uniform", "fit", "taper", "split")[kind]
+        return d
 
     def genotype_query(self, query, strict=False, strip_cr=False):
         q = query.encode() if isinstance(query, str) else query
