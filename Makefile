@@ -8,8 +8,8 @@ ARCH ?= gfx950
 B := build
 GPU_SRC := vcfx_amd/csrc/gpu
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Iinclude -I$(GPU_SRC) $(EXTRA_HIPFLAGS)
-GPU_OBJS := $(B)/obj/vcfxg_kernels.o $(B)/obj/vcfxg_rf.o $(B)/obj/vcfxg_ld.o $(B)/obj/vcfxg_ld_fast.o $(B)/obj/vcfxg_ld_mask.o $(B)/obj/vcfxg_af_walk.o $(B)/obj/vcfxg_fq_walk.o $(B)/obj/vcfxg_hwe.o $(B)/obj/vcfxg_dose.o $(B)/obj/vcfxg_md.o $(B)/obj/vcfxg_ac.o $(B)/obj/vcfxg_ph.o $(B)/obj/vcfxg_ib.o $(B)/obj/vcfxg_sx.o $(B)/obj/vcfxg_cc.o $(B)/obj/vcfxg_dd.o $(B)/obj/vcfxg_ms.o $(B)/obj/vcfxg_fa.o $(B)/obj/vcfxg_srt.o $(B)/obj/vcfxg_df.o $(B)/obj/vcfxg_mg.o $(B)/obj/vcfxg_inflate.o $(B)/obj/vcfxg_decimal.o \
-            $(patsubst %,$(B)/obj/vcfxg_%.o,api api_bgzf api_walk api_af api_fq api_hwe api_ib api_cc api_dd api_ms api_fa api_srt api_df api_mg api_dose api_lines api_ld comm)
+GPU_OBJS := $(B)/obj/vcfxg_kernels.o $(B)/obj/vcfxg_rf.o $(B)/obj/vcfxg_ld.o $(B)/obj/vcfxg_ld_fast.o $(B)/obj/vcfxg_ld_mask.o $(B)/obj/vcfxg_af_walk.o $(B)/obj/vcfxg_fq_walk.o $(B)/obj/vcfxg_hwe.o $(B)/obj/vcfxg_dose.o $(B)/obj/vcfxg_md.o $(B)/obj/vcfxg_ac.o $(B)/obj/vcfxg_ph.o $(B)/obj/vcfxg_ib.o $(B)/obj/vcfxg_sx.o $(B)/obj/vcfxg_cc.o $(B)/obj/vcfxg_dd.o $(B)/obj/vcfxg_ms.o $(B)/obj/vcfxg_fa.o $(B)/obj/vcfxg_srt.o $(B)/obj/vcfxg_df.o $(B)/obj/vcfxg_mg.o $(B)/obj/vcfxg_gather.o $(B)/obj/vcfxg_inflate.o $(B)/obj/vcfxg_decimal.o \
+            $(patsubst %,$(B)/obj/vcfxg_%.o,api api_bgzf api_walk api_af api_fq api_hwe api_ib api_cc api_dd api_ms api_fa api_srt api_df api_mg api_keyed api_dose api_lines api_ld comm)
 
 TOOLS := VCFX_allele_freq_calc VCFX_genotype_query VCFX_record_filter VCFX_variant_counter VCFX_ld_calculator \
          VCFX_nonref_filter VCFX_hwe_tester VCFX_dosage_calculator VCFX_missing_detector VCFX_allele_counter \
@@ -115,8 +115,6 @@ sanitize: $(SAN)/host_san_asan $(SAN)/host_san_tsan $(SAN)/core_api_asan $(SAN)/
     $(if $(wildcard tests/host_lines_test.cpp),$(SAN)/host_lines $(SAN)/host_lines_asan) \
     $(if $(wildcard tests/host_ms_test.cpp),$(SAN)/host_ms_asan) \
     $(if $(wildcard tests/host_fa_test.cpp),$(SAN)/host_fa_asan) \
-    $(if $(wildcard tests/host_df_test.cpp),$(SAN)/host_df_asan) \
-    $(if $(wildcard tests/host_mg_test.cpp),$(SAN)/host_mg_asan) \
     $(if $(wildcard tests/decimal_bounds_test.cpp),$(SAN)/decimal_bounds_asan) \
     $(if $(wildcard tests/walk_layout_test.cpp),$(SAN)/walk_layout_asan)
 $(SAN)/host_san_asan: $(SAN_HOST_SRC) $(wildcard $(HOST_SRC)/*.h) $(B)/libvcfx_gpu.so
@@ -163,14 +161,16 @@ $(SAN)/host_ms_asan: tests/host_ms_test.cpp $(TOOL_SRC)/ms_host.h include/vcfx_g
 $(SAN)/host_fa_asan: tests/host_fa_test.cpp $(TOOL_SRC)/fa_host.h include/vcfx_gpu.h
 	@mkdir -p $(dir $@)
 	$(CXX) $(SANFLAGS) -I$(TOOL_SRC) -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
-# VCFX_diff_tool's host-only code (the two files as one text, the walk over a side's text blocks:
-# df_host.h) under ASan + UBSan
-$(SAN)/host_df_asan: tests/host_df_test.cpp $(TOOL_SRC)/df_host.h
+# VCFX_diff_tool's host-only code (the two files as one text: df_host.h; the loop over a side's text
+# blocks: tools.h) under ASan + UBSan.  This program and VCFX_merger's are built by their own tests
+# (tests/test_host_df.py, tests/test_host_mg.py), not by `sanitize`: they compile a header that several
+# tools share, and a mismatch there must not stop the input layer's and the runner's sanitizer builds.
+$(SAN)/host_df_asan: tests/host_df_test.cpp $(TOOL_SRC)/df_host.h $(TOOL_SRC)/tools.h
 	@mkdir -p $(dir $@)
 	$(CXX) $(SANFLAGS) -I$(TOOL_SRC) -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
-# VCFX_merger's host-only code (the K files as one text, the split of -m values: mg_host.h) under
-# ASan + UBSan
-$(SAN)/host_mg_asan: tests/host_mg_test.cpp $(TOOL_SRC)/mg_host.h
+# VCFX_merger's host-only code (the K files as one text, the split of -m values: mg_host.h; the loop
+# over the text blocks: tools.h) under ASan + UBSan
+$(SAN)/host_mg_asan: tests/host_mg_test.cpp $(TOOL_SRC)/mg_host.h $(TOOL_SRC)/tools.h
 	@mkdir -p $(dir $@)
 	$(CXX) $(SANFLAGS) -I$(TOOL_SRC) -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
 # threshold_bounds (vcfxg_decimal.cpp: plain C++, no HIP) under ASan + UBSan: doubles' bit patterns in,

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "df_host.h"
+#include "tools.h"
 
 using namespace vcfxh;
 
@@ -108,7 +109,7 @@ static void walks() {
     for (auto &k : keys) all += k + "\n";
     for (uint64_t cap : {1ull, 8ull, 64ull, 100ull, 4096ull, 1ull << 30}) {
         Side s{keys, cap};
-        const bool ok = df_walk_side(keys.size(), [&](uint64_t f, uint64_t *t, uint64_t *b) { return s(f, t, b); },
+        const bool ok = write_text_blocks(keys.size(), [&](uint64_t f, uint64_t *t, uint64_t *b) { return s(f, t, b); },
                                      [&](uint64_t bytes) {
                                          CHECK(bytes == s.text.size());
                                          s.written += s.text;
@@ -121,18 +122,18 @@ static void walks() {
     }
     // no key: no call at all
     int calls = 0;
-    CHECK(df_walk_side(0, [&](uint64_t, uint64_t *, uint64_t *) { return ++calls, true; }, [&](uint64_t) { return ++calls, true; }));
+    CHECK(write_text_blocks(0, [&](uint64_t, uint64_t *, uint64_t *) { return ++calls, true; }, [&](uint64_t) { return ++calls, true; }));
     CHECK(calls == 0);
     // a failed call, a failed write, a block of no key and a block past the end all stop the walk
-    CHECK(!df_walk_side(5, [&](uint64_t, uint64_t *, uint64_t *) { return false; }, [&](uint64_t) { return true; }));
+    CHECK(!write_text_blocks(5, [&](uint64_t, uint64_t *, uint64_t *) { return false; }, [&](uint64_t) { return true; }));
     calls = 0;
-    CHECK(!df_walk_side(5, [&](uint64_t, uint64_t *t, uint64_t *) { return *t = 1, true; }, [&](uint64_t) { return ++calls < 3; }));
+    CHECK(!write_text_blocks(5, [&](uint64_t, uint64_t *t, uint64_t *) { return *t = 1, true; }, [&](uint64_t) { return ++calls < 3; }));
     CHECK(calls == 3);
     calls = 0;
-    CHECK(!df_walk_side(5, [&](uint64_t, uint64_t *t, uint64_t *) { return ++calls, *t = 0, true; }, [&](uint64_t) { return true; }));
+    CHECK(!write_text_blocks(5, [&](uint64_t, uint64_t *t, uint64_t *) { return ++calls, *t = 0, true; }, [&](uint64_t) { return true; }));
     CHECK(calls == 1);
-    CHECK(!df_walk_side(5, [&](uint64_t f, uint64_t *t, uint64_t *) { return *t = f ? 4 : 2, true; }, [&](uint64_t) { return true; }));
-    CHECK(df_walk_side(5, [&](uint64_t f, uint64_t *t, uint64_t *) { return *t = f ? 3 : 2, true; }, [&](uint64_t) { return true; }));
+    CHECK(!write_text_blocks(5, [&](uint64_t f, uint64_t *t, uint64_t *) { return *t = f ? 4 : 2, true; }, [&](uint64_t) { return true; }));
+    CHECK(write_text_blocks(5, [&](uint64_t f, uint64_t *t, uint64_t *) { return *t = f ? 3 : 2, true; }, [&](uint64_t) { return true; }));
 }
 
 int main() {

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "mg_host.h"
+#include "tools.h"
 
 using namespace vcfxh;
 
@@ -128,7 +129,7 @@ static void walks() {
     for (uint64_t lines : {0ull, 1ull, 2ull, 7ull, 64ull, 100ull})
         for (uint64_t per : {1ull, 2ull, 7ull, 1000ull}) {
             uint64_t next = 0, calls = 0, written = 0;
-            const bool ok = mg_walk_blocks(
+            const bool ok = write_text_blocks(
                 lines,
                 [&](uint64_t first, uint64_t *taken, uint64_t *bytes) {
                     CHECK(first == next);
@@ -144,11 +145,11 @@ static void walks() {
                 });
             CHECK(ok && next == lines && written == 10 * lines && calls == (lines + per - 1) / per);
         }
-    CHECK(!mg_walk_blocks(3, [](uint64_t, uint64_t *, uint64_t *) { return false; }, [](uint64_t) { return true; }));
-    CHECK(!mg_walk_blocks(3, [](uint64_t, uint64_t *t, uint64_t *) { *t = 0; return true; }, [](uint64_t) { return true; }));
-    CHECK(!mg_walk_blocks(3, [](uint64_t, uint64_t *t, uint64_t *) { *t = 4; return true; }, [](uint64_t) { return true; }));
-    CHECK(!mg_walk_blocks(3, [](uint64_t, uint64_t *t, uint64_t *) { *t = 1; return true; }, [](uint64_t) { return false; }));
-    CHECK(mg_walk_blocks(0, [](uint64_t, uint64_t *, uint64_t *) { return false; }, [](uint64_t) { return false; }));
+    CHECK(!write_text_blocks(3, [](uint64_t, uint64_t *, uint64_t *) { return false; }, [](uint64_t) { return true; }));
+    CHECK(!write_text_blocks(3, [](uint64_t, uint64_t *t, uint64_t *) { *t = 0; return true; }, [](uint64_t) { return true; }));
+    CHECK(!write_text_blocks(3, [](uint64_t, uint64_t *t, uint64_t *) { *t = 4; return true; }, [](uint64_t) { return true; }));
+    CHECK(!write_text_blocks(3, [](uint64_t, uint64_t *t, uint64_t *) { *t = 1; return true; }, [](uint64_t) { return false; }));
+    CHECK(write_text_blocks(0, [](uint64_t, uint64_t *, uint64_t *) { return false; }, [](uint64_t) { return false; }));
 }
 
 int main() {

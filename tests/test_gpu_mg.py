@@ -216,6 +216,22 @@ def test_bytes_and_pos_forms(eng):
     assert res[0].statuses.count(R.BAD) >= 12 and res[0].hdr == 1
 
 
+# POS fields at the edges of long, which std::stol's restatement on the device tells apart by the
+# exact 64-bit overflow test of the C integer front end it shares with the sorter
+POS_EDGES = [b"9223372036854775807", b"9223372036854775808", b"-9223372036854775808", b"-9223372036854775809"]
+
+
+@pytest.mark.parametrize("pos", POS_EDGES, ids=[p.decode() for p in POS_EDGES])
+def test_long_limits_on_one_line(eng, pos):
+    """a header and one data line, then two files of one line each: the first value outside long is
+    BAD, the last one inside it is kept and ordered as itself"""
+    line = rec(b"p", pos) + b"\n"
+    inside = -2 ** 63 <= int(pos) < 2 ** 63
+    for files in ([R.HDR + line], [R.HDR + line, rec(b"p", b"-1") + b"\n"]):
+        res = check_engine(eng, files)
+        assert res[0].statuses.count(R.BAD) == (0 if inside else 1)
+
+
 @pytest.mark.parametrize("n", [1, 255, 256, 257, 4097])
 def test_kept_line_counts(eng, n):
     """kept lines around the wave, the block and the sort's tiles, dealt into three files (unsorted:

@@ -243,6 +243,24 @@ def test_small_text_blocks(block, tmp_path, monkeypatch):
     assert _run_bin([TOOL, str(path)], env={"VCFXG_SRT_BLOCK": str(block)}) == R.run([TOOL, str(path)])
 
 
+# POS fields at the edges of std::stoi's grammar and of int, which the stdin mode reads through the
+# 64-bit C integer front end it shares with the merger and the duplicate remover (" \t7": the field
+# is the blank before the tab)
+POS_EDGES = [b"2147483647", b"2147483648", b"-2147483648", b"-2147483649", b"9223372036854775808",
+             b"99999999999999999999", b"+5", b" \t7", b"", b"-"]
+
+
+@pytest.mark.parametrize("pos", POS_EDGES, ids=[repr(p.decode()) for p in POS_EDGES])
+def test_pos_edges_on_one_line(eng, pos):
+    """a header and one data line (and the same line after a line that sorts on either side of any
+    int): statuses, order and text of both modes against the restatement of std::stoi"""
+    line = R.record(b"1", pos) + b"\n"
+    for buf in (R.HDR + line, R.HDR + R.record(b"1", b"0") + b"\n" + line):
+        check_engine(eng, buf)
+    want = R.stoi(pos.split(b"\t")[0])
+    assert R.statuses(R.HDR + line, True)[0][-1] == (R.BAD if want is None else R.KEPT)
+
+
 def test_sorted_reversed_and_equal_inputs(eng, tmp_path):
     buf = R.gen_vcf(5, 1500, pad=60)
     lines = R.sort_bytes(buf, False)[0].split(b"\n")[2:-1]

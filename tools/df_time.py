@@ -272,7 +272,7 @@ def merge_trace(path):
     with open(path) as f:
         for r in csv.DictReader(f):
             name = r.get("Name") or r.get("KernelName") or ""
-            if "k_df_" in name or "k_srt_gather" in name:
+            if "k_df_" in name or "k_text_gather" in name:
                 short = name.split("(")[0].split("::")[-1]
                 rows[short] = {"calls": int(r["Calls"]), "total_us": round(float(r["TotalDurationNs"]) / 1e3, 1),
                                "average_us": round(float(r["AverageNs"]) / 1e3, 1)}

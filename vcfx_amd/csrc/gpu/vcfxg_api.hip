@@ -210,8 +210,14 @@ void vcfxg_close(vcfxg_ctx *c) {
     for (DevBuf *b : {&c->input, &c->idx_counts, &c->idx_offs, &c->idx_pos, &c->line_end, &c->d_nlines, &c->scan_tmp, &c->alt,
                       &c->tot, &c->rowpre, &c->status, &c->rowlen, &c->rowoff, &c->text, &c->counters, &c->query, &c->crit, &c->pool, &c->ld_G, &c->ld_lines,
                       &c->ld_vidx, &c->ld_valid, &c->ld_Gc, &c->ld_wcnt, &c->ld_wval, &c->ld_vbase, &c->ld_small, &c->ld_pend, &c->ld_vars, &c->ld_plen, &c->ld_poff, &c->ld_prefix,
-                      &c->ld_cid, &c->ld_blocks, &c->ld_cnt, &c->ld_off, &c->ld_pairs, &c->ld_fast, &c->ld_gflag, &c->ld_Gp, &c->ld_Gv, &c->ld_Gq, &c->dose_meta, &c->af_meta, &c->ld_temp, &c->ld_quarters, &c->ld_stage_ctr, &c->ld_rowoff, &c->async_small, &c->wk_le, &c->wk_alt, &c->wk_tot, &c->wk_rowpre, &c->wk_status, &c->wk_meta, &c->wk_count, &c->wk_offs, &c->wk_gt, &c->wk_small, &c->wk_tabs, &c->rf_tabs, &c->hwe_aux, &c->wk_aux, &c->hwe_rc, &c->wk_text, &c->wk_toff, &c->wk_start, &c->wk_cx, &c->wk_bs, &c->scratch_small, &c->byte_cnt, &c->ld_moff, &c->ld_midx, &c->ld_mvar, &c->ld_gt16, &c->ld_sprec, &c->ld_midx16, &c->bgz_in, &c->bgz_mem, &c->bgz_off, &c->bgz_stat, &c->bgz_small, &c->bgz_perm, &c->ib_codes, &c->ib_meta, &c->ib_tab, &c->ib_packed, &c->ib_cnt, &c->ib_offs, &c->ib_sum, &c->ib_obs, &c->ib_used, &c->ib_carried, &c->ib_small, &c->sx_mask, &c->cc_mult, &c->cc_isdata, &c->cc_ord, &c->cc_chrom, &c->cc_small, &c->dd_tabs, &c->dd_pos, &c->dd_hash, &c->dd_queue, &c->dd_isdata, &c->dd_ord, &c->dd_k0, &c->dd_k1, &c->dd_v0, &c->dd_v1, &c->dd_tmp, &c->dd_hp, &c->dd_head, &c->dd_left, &c->srt_pos, &c->srt_aux, &c->srt_w0, &c->srt_queue, &c->srt_written, &c->srt_ord, &c->srt_k0, &c->srt_k1, &c->srt_v0, &c->srt_v1, &c->srt_tmp, &c->srt_len, &c->srt_off, &c->srt_src, &c->df_tabs, &c->df_klen, &c->df_koff, &c->df_ntok, &c->df_posv, &c->df_natv, &c->df_nsuf, &c->df_hash, &c->df_isdata, &c->df_ord, &c->df_queue, &c->df_ktext, &c->df_line, &c->df_k0, &c->df_k1, &c->df_v0, &c->df_v1, &c->df_tmp, &c->df_hp, &c->df_head, &c->df_rep, &c->df_first2, &c->df_left, &c->df_state, &c->df_uflag, &c->df_uord, &c->df_len, &c->df_off, &c->df_src, &c->df_sum, &c->mg_file, &c->mg_pos, &c->mg_w0, &c->mg_ks, &c->mg_kl, &c->mg_pn, &c->mg_num, &c->mg_queue, &c->mg_written, &c->mg_ord, &c->mg_fmeta, &c->mg_k0, &c->mg_k1, &c->mg_v0, &c->mg_v1, &c->mg_tmp, &c->mg_len, &c->mg_off, &c->mg_src, &c->mg_state, &c->fa_flag, &c->fa_col, &c->fa_meta, &c->fa_M, &c->fa_rowoff, &c->fa_skip})
+                      &c->ld_cid, &c->ld_blocks, &c->ld_cnt, &c->ld_off, &c->ld_pairs, &c->ld_fast, &c->ld_gflag, &c->ld_Gp, &c->ld_Gv, &c->ld_Gq, &c->dose_meta, &c->af_meta, &c->ld_temp, &c->ld_quarters, &c->ld_stage_ctr, &c->ld_rowoff, &c->async_small, &c->wk_le, &c->wk_alt, &c->wk_tot, &c->wk_rowpre, &c->wk_status, &c->wk_meta, &c->wk_count, &c->wk_offs, &c->wk_gt, &c->wk_small, &c->wk_tabs, &c->rf_tabs, &c->hwe_aux, &c->wk_aux, &c->hwe_rc, &c->wk_text, &c->wk_toff, &c->wk_start, &c->wk_cx, &c->wk_bs, &c->scratch_small, &c->byte_cnt, &c->ld_moff, &c->ld_midx, &c->ld_mvar, &c->ld_gt16, &c->ld_sprec, &c->ld_midx16, &c->bgz_in, &c->bgz_mem, &c->bgz_off, &c->bgz_stat, &c->bgz_small, &c->bgz_perm, &c->ib_codes, &c->ib_meta, &c->ib_tab, &c->ib_packed, &c->ib_cnt, &c->ib_offs, &c->ib_sum, &c->ib_obs, &c->ib_used, &c->ib_carried, &c->ib_small, &c->sx_mask, &c->cc_mult, &c->cc_isdata, &c->cc_ord, &c->cc_chrom, &c->cc_small, &c->dd_tabs, &c->dd_pos, &c->dd_hash, &c->dd_queue, &c->dd_isdata, &c->dd_ord, &c->dd_hp, &c->dd_head, &c->dd_left, &c->srt_pos, &c->srt_aux, &c->srt_w0, &c->srt_queue, &c->srt_written, &c->srt_ord, &c->df_tabs, &c->df_klen, &c->df_koff, &c->df_ntok, &c->df_posv, &c->df_natv, &c->df_nsuf, &c->df_hash, &c->df_isdata, &c->df_ord, &c->df_queue, &c->df_ktext, &c->df_line, &c->df_hp, &c->df_head, &c->df_rep, &c->df_first2, &c->df_left, &c->df_state, &c->df_uflag, &c->df_uord, &c->df_sum, &c->mg_file, &c->mg_pos, &c->mg_w0, &c->mg_ks, &c->mg_kl, &c->mg_pn, &c->mg_num, &c->mg_queue, &c->mg_written, &c->mg_ord, &c->mg_fmeta, &c->mg_state, &c->fa_flag, &c->fa_col, &c->fa_meta, &c->fa_M, &c->fa_rowoff, &c->fa_skip})
         if (b->p) (void)hipFree(b->p);
+    for (SortScratch *s : {&c->dd_sort, &c->srt_sort, &c->df_sort, &c->mg_sort})
+        for (DevBuf *b : {&s->k0, &s->k1, &s->v0, &s->v1, &s->tmp})
+            if (b->p) (void)hipFree(b->p);
+    for (TextOrder *t : {&c->srt_out, &c->df_out, &c->mg_out})
+        for (DevBuf *b : {&t->len, &t->off, &t->src})
+            if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : c->bgz_tok)
         if (b.p) (void)hipFree(b.p);
     if (c->af_small.p) (void)hipFree(c->af_small.p);

@@ -58,33 +58,28 @@ int vcfxg_dedup(vcfxg_ctx *c, int mode, const vcfxg_dd_params *p, vcfxg_summary 
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const uint64_t nd = nd_host;
     if (nd) {
-        r = ensure(c, c->dd_k0, 8 * nd);
-        if (!r) r = ensure(c, c->dd_k1, 8 * nd);
-        if (!r) r = ensure(c, c->dd_v0, 4 * nd);
-        if (!r) r = ensure(c, c->dd_v1, 4 * nd);
+        SortScratch &S = c->dd_sort;
+        r = sort_begin(c, S, nd);
         if (!r) r = ensure(c, c->dd_hp, 4 * nd);
         if (!r) r = ensure(c, c->dd_head, 4 * nd);
         if (!r) r = ensure(c, c->dd_left, nd);
         if (r) return r;
-        uint64_t *k0 = P<uint64_t>(c->dd_k0), *k1 = P<uint64_t>(c->dd_k1);
-        uint32_t *v0 = P<uint32_t>(c->dd_v0), *v1 = P<uint32_t>(c->dd_v1);
         uint32_t *hp = P<uint32_t>(c->dd_hp), *head = P<uint32_t>(c->dd_head);
-        const int end_bit = p->hash_bits ? (int)p->hash_bits : 64;
-        size_t t_sort = 0, t_scan = 0;
-        HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(nullptr, t_sort, k0, k1, v0, v1, (int)nd, 0, end_bit, c->stream));
+        size_t t_scan = 0;
         HIPCHK(c, hipcub::DeviceScan::InclusiveScan(nullptr, t_scan, hp, head, hipcub::Max(), (int)nd, c->stream));
-        r = ensure(c, c->dd_tmp, std::max(t_sort, t_scan));
+        r = ensure(c, S.tmp, std::max(S.t_sort, t_scan));
         if (r) return r;
         HIPCHK(c, vcfxg::launch_dd_gather(L, P<uint32_t>(c->dd_isdata), P<uint64_t>(c->dd_ord), P<uint64_t>(c->dd_hash),
-                                          p->hash_bits, k0, v0, c->stream));
-        HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(c->dd_tmp.p, t_sort, k0, k1, v0, v1, (int)nd, 0, end_bit, c->stream));
+                                          p->hash_bits, S.ka, S.va, c->stream));
+        r = sort_pass(c, S, nd, p->hash_bits ? (int)p->hash_bits : 64);
+        if (r) return r;
         prof_end(c, "dd_sort");
         prof_begin(c, "dd_verify");
-        HIPCHK(c, vcfxg::launch_dd_heads(nd, k1, hp, c->stream));
-        HIPCHK(c, hipcub::DeviceScan::InclusiveScan(c->dd_tmp.p, t_scan, hp, head, hipcub::Max(), (int)nd, c->stream));
+        HIPCHK(c, vcfxg::launch_dd_heads(nd, S.ka, hp, c->stream));
+        HIPCHK(c, hipcub::DeviceScan::InclusiveScan(S.tmp.p, t_scan, hp, head, hipcub::Max(), (int)nd, c->stream));
         HIPCHK(c, hipMemsetAsync(c->dd_left.p, 0, nd, c->stream));
         HIPCHK(c, vcfxg::launch_dd_verify(buf, (int64_t)c->data_start, le, stdin_mode, P<uint64_t>(c->dd_tabs),
-                                          P<int32_t>(c->dd_pos), nd, k1, v1, head, P<uint8_t>(c->status),
+                                          P<int32_t>(c->dd_pos), nd, S.ka, S.va, head, P<uint8_t>(c->status),
                                           P<uint8_t>(c->dd_left), counters, c->stream));
         prof_end(c, "dd_verify");
     } else {
@@ -108,14 +103,7 @@ int vcfxg_dedup(vcfxg_ctx *c, int mode, const vcfxg_dd_params *p, vcfxg_summary 
 }
 
 int vcfxg_dedup_status(vcfxg_ctx *c, uint64_t first, uint64_t count, uint8_t *status) {
-    if (!c || (!status && count)) return VCFXG_E_ARG;
-    if (!c->indexed || !c->dd_done) return VCFXG_E_STATE;
-    if (first > c->n_lines || count > c->n_lines - first) return VCFXG_E_ARG;
-    if (!count) return VCFXG_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(status, P<uint8_t>(c->status) + first, count, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VCFXG_OK;
+    return c ? fetch_status(c, c->dd_done, first, count, status) : VCFXG_E_ARG;
 }
 
 int vcfxg_dedup_counts(const vcfxg_ctx *c, uint64_t counts[6]) {

@@ -29,8 +29,9 @@ int vcfxg_diff(vcfxg_ctx *c, const vcfxg_df_params *p, vcfxg_summary *out) {
     if (L >= (1ull << 31)) return VCFXG_E_ARG;  // (the scans and the sort count their items in an int)
     HIPCHK(c, hipSetDevice(c->device));
     c->df_done = false;
-    c->df_nu = c->df_nu1 = 0;
-    c->df_off_host.clear();
+    c->df_nu1 = 0;
+    c->df_out.n = 0;
+    c->df_out.off_host.clear();
     std::memset(c->df_counts, 0, sizeof c->df_counts);
     const int sorted = p->assume_sorted ? 1 : 0, natural = sorted && p->natural ? 1 : 0;
     c->df_counts[6] = sorted ? VCFXG_DF_PATH_BOUNDS : VCFXG_DF_PATH_HASH;
@@ -94,33 +95,28 @@ int vcfxg_diff(vcfxg_ctx *c, const vcfxg_df_params *p, vcfxg_summary *out) {
         prof_end(c, "df_text");
         if (!sorted) {
             prof_begin(c, "df_sort");
-            r = ensure(c, c->df_k0, 8 * nd);
-            if (!r) r = ensure(c, c->df_k1, 8 * nd);
-            if (!r) r = ensure(c, c->df_v0, 4 * nd);
-            if (!r) r = ensure(c, c->df_v1, 4 * nd);
+            SortScratch &S = c->df_sort;
+            r = sort_begin(c, S, nd);
             if (!r) r = ensure(c, c->df_hp, 4 * nd);
             if (!r) r = ensure(c, c->df_head, 4 * nd);
             if (!r) r = ensure(c, c->df_rep, 4 * nd);
             if (!r) r = ensure(c, c->df_first2, 4 * nd);
             if (!r) r = ensure(c, c->df_left, nd);
             if (r) return r;
-            uint64_t *k0 = P<uint64_t>(c->df_k0), *k1 = P<uint64_t>(c->df_k1);
-            uint32_t *v0 = P<uint32_t>(c->df_v0), *v1 = P<uint32_t>(c->df_v1);
             uint32_t *hp = P<uint32_t>(c->df_hp), *hd = P<uint32_t>(c->df_head);
-            const int end_bit = p->hash_bits ? (int)p->hash_bits : 64;
-            size_t t_sort = 0, t_scan = 0;
-            HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(nullptr, t_sort, k0, k1, v0, v1, (int)nd, 0, end_bit, c->stream));
+            size_t t_scan = 0;
             HIPCHK(c, hipcub::DeviceScan::InclusiveScan(nullptr, t_scan, hp, hd, hipcub::Max(), (int)nd, c->stream));
-            r = ensure(c, c->df_tmp, std::max(t_sort, t_scan));
+            r = ensure(c, S.tmp, std::max(S.t_sort, t_scan));
             if (r) return r;
-            HIPCHK(c, vcfxg::launch_df_pairs(nd, line, P<uint64_t>(c->df_hash), p->hash_bits, k0, v0, c->stream));
-            HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(c->df_tmp.p, t_sort, k0, k1, v0, v1, (int)nd, 0, end_bit, c->stream));
+            HIPCHK(c, vcfxg::launch_df_pairs(nd, line, P<uint64_t>(c->df_hash), p->hash_bits, S.ka, S.va, c->stream));
+            r = sort_pass(c, S, nd, p->hash_bits ? (int)p->hash_bits : 64);
+            if (r) return r;
             prof_end(c, "df_sort");
             prof_begin(c, "df_classes");
-            HIPCHK(c, vcfxg::launch_dd_heads(nd, k1, hp, c->stream));
-            HIPCHK(c, hipcub::DeviceScan::InclusiveScan(c->df_tmp.p, t_scan, hp, hd, hipcub::Max(), (int)nd, c->stream));
+            HIPCHK(c, vcfxg::launch_dd_heads(nd, S.ka, hp, c->stream));
+            HIPCHK(c, hipcub::DeviceScan::InclusiveScan(S.tmp.p, t_scan, hp, hd, hipcub::Max(), (int)nd, c->stream));
             HIPCHK(c, hipMemsetAsync(c->df_left.p, 0, nd, c->stream));
-            HIPCHK(c, vcfxg::launch_df_classes(P<char>(c->df_ktext), koff, D.klen, nd, k1, v1, hd, P<uint32_t>(c->df_rep),
+            HIPCHK(c, vcfxg::launch_df_classes(P<char>(c->df_ktext), koff, D.klen, nd, S.ka, S.va, hd, P<uint32_t>(c->df_rep),
                                                P<uint32_t>(c->df_first2), P<uint8_t>(c->df_left), D.status, counters,
                                                c->stream));
             prof_end(c, "df_classes");
@@ -161,19 +157,17 @@ int vcfxg_diff(vcfxg_ctx *c, const vcfxg_df_params *p, vcfxg_summary *out) {
     HIPCHK(c, hipMemcpyAsync(sum, c->df_sum.p, sizeof sum, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const uint64_t nu = sum[0] + sum[1];
-    r = ensure(c, c->df_len, 8 * (nu + 1));
-    if (!r) r = ensure(c, c->df_off, 8 * (nu + 1));
-    if (!r) r = ensure(c, c->df_src, 8 * (nu + 1));
+    TextOrder &T = c->df_out;
+    r = place_begin(c, T, nu);
     if (r) return r;
-    HIPCHK(c, vcfxg::launch_df_place(L, uflag, uord, koff, D.klen, P<uint64_t>(c->df_len), P<uint64_t>(c->df_src), c->stream));
-    r = exclusive_scan(c, P<uint64_t>(c->df_len), P<uint64_t>(c->df_off), (size_t)nu + 1);
+    HIPCHK(c, vcfxg::launch_df_place(L, uflag, uord, koff, D.klen, P<uint64_t>(T.len), P<uint64_t>(T.src), c->stream));
+    r = exclusive_scan(c, P<uint64_t>(T.len), P<uint64_t>(T.off), (size_t)nu + 1);
     if (r) return r;
     prof_end(c, "df_place");
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
     for (int i = 0; i < 8; i++)
         if (i != 6) c->df_counts[i] = sum[i];
-    c->df_nu = nu;
     c->df_nu1 = sum[0];
     c->df_done = true;
     if (out) {
@@ -187,14 +181,7 @@ int vcfxg_diff(vcfxg_ctx *c, const vcfxg_df_params *p, vcfxg_summary *out) {
 }
 
 int vcfxg_diff_status(vcfxg_ctx *c, uint64_t first, uint64_t count, uint8_t *status) {
-    if (!c || (!status && count)) return VCFXG_E_ARG;
-    if (!c->indexed || !c->df_done) return VCFXG_E_STATE;
-    if (first > c->n_lines || count > c->n_lines - first) return VCFXG_E_ARG;
-    if (!count) return VCFXG_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(status, P<uint8_t>(c->status) + first, count, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VCFXG_OK;
+    return c ? fetch_status(c, c->df_done, first, count, status) : VCFXG_E_ARG;
 }
 
 int vcfxg_diff_counts(const vcfxg_ctx *c, uint64_t counts[8]) {
@@ -203,42 +190,16 @@ int vcfxg_diff_counts(const vcfxg_ctx *c, uint64_t counts[8]) {
     return VCFXG_OK;
 }
 
-// Keys [first_out, first_out + k) of one side's output: as many as fit df_block bytes, one at least
-// (the offsets are read back once per diff; the cut is a search in them), gathered into the text by
-// the sorter's gather over the key text.
+// Keys [first_out, first_out + k) of one side's output: as many as fit df_block bytes, one at least,
+// gathered into the text from the key text.
 int vcfxg_diff_text(vcfxg_ctx *c, int side, uint64_t first_out, uint64_t *taken, uint64_t *bytes) {
     if (!c || (side != 0 && side != 1)) return VCFXG_E_ARG;
     if (taken) *taken = 0;
     if (bytes) *bytes = 0;
     if (!c->indexed || !c->df_done) return VCFXG_E_STATE;
-    const uint64_t lo = side ? c->df_nu1 : 0, hi = side ? c->df_nu : c->df_nu1;
+    const uint64_t lo = side ? c->df_nu1 : 0, hi = side ? c->df_out.n : c->df_nu1;
     if (first_out > hi - lo) return VCFXG_E_ARG;
-    c->text_bytes = 0;
-    const uint64_t first = lo + first_out;
-    if (first == hi) return VCFXG_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const uint64_t nu = c->df_nu;
-    if (c->df_off_host.size() != nu + 1) {
-        c->df_off_host.resize(nu + 1);
-        HIPCHK(c, hipMemcpyAsync(c->df_off_host.data(), c->df_off.p, 8 * (nu + 1), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    const uint64_t *off = c->df_off_host.data();
-    uint64_t k = (uint64_t)(std::upper_bound(off + first + 1, off + hi + 1, off[first] + c->df_block) - (off + first + 1));
-    if (!k) k = 1;
-    const uint64_t n = off[first + k] - off[first];
-    int r = ensure(c, c->text, n + 32);
-    if (r) return r;
-    prof_begin(c, "df_gather");
-    HIPCHK(c, vcfxg::launch_srt_gather(P<char>(c->df_ktext), P<uint64_t>(c->df_off), P<uint64_t>(c->df_src), first, k, n,
-                                       c->srt_nt, P<char>(c->text), c->stream));
-    prof_end(c, "df_gather");
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    c->text_bytes = n;
-    if (taken) *taken = k;
-    if (bytes) *bytes = n;
-    return VCFXG_OK;
+    return text_block(c, c->df_out, P<char>(c->df_ktext), lo + first_out, hi, c->df_block, "df_gather", taken, bytes);
 }
 
 }  // extern "C"

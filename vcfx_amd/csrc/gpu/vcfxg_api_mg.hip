@@ -1,6 +1,4 @@
 // vcfxg_api_mg.hip -- VCFX_merger (the C ABI of include/vcfx_gpu.h)
-#include <hipcub/hipcub.hpp>
-
 #include "vcfxg_ctx.h"
 
 using namespace vcfxg;
@@ -10,15 +8,6 @@ static_assert(vcfxg::kMgEmpty == VCFXG_MG_EMPTY && vcfxg::kMgKept == VCFXG_MG_KE
                   vcfxg::kMgWindow == VCFXG_MG_WINDOW,
               "merger line statuses");
 
-static int mg_bits(uint64_t x) {
-    int b = 0;
-    while (x) {
-        b++;
-        x >>= 1;
-    }
-    return b;
-}
-
 extern "C" {
 
 // The files' first lines, the key pass and the class pass over every indexed line, the written
@@ -26,10 +15,10 @@ extern "C" {
 // the longest key string, which size the sort).  -s: the ordered check (a synchronisation for its
 // flag).  Sort path: hipcub's stable radix sort, least significant part first (POS, the key
 // string's length, its words from the last to the first; natural: then num and the prefix), each
-// part gathered through the order so far; every bit range starts at 0 (the sorter's finding about
-// the library's merge path).  Walk path: launch after launch of at most mg_walk_steps steps: a step
-// writes a line, so ceil(kept lines / steps) launches end it, with no host read between them.  Then
-// the output lines' lengths and their scan.
+// part gathered through the order so far; every bit range starts at 0 (sort_string_words).  Walk
+// path: launch after launch of at most mg_walk_steps steps: a step writes a line, so ceil(kept
+// lines / steps) launches end it, with no host read between them.  Then the output lines' lengths
+// and their scan.
 int vcfxg_merge(vcfxg_ctx *c, const vcfxg_mg_params *p, vcfxg_summary *out) {
     if (!c || !p || !p->file_start || !p->n_files) return VCFXG_E_ARG;
     if (!c->indexed) return VCFXG_E_STATE;
@@ -42,9 +31,9 @@ int vcfxg_merge(vcfxg_ctx *c, const vcfxg_mg_params *p, vcfxg_summary *out) {
     if (L >= (1ull << 31)) return VCFXG_E_ARG;  // (the scans and the sort count their items in an int)
     HIPCHK(c, hipSetDevice(c->device));
     c->mg_done = false;
-    c->mg_nw = 0;
+    c->mg_out.n = 0;
+    c->mg_out.off_host.clear();
     c->mg_files = K;
-    c->mg_off_host.clear();
     std::memset(c->mg_counts, 0, sizeof c->mg_counts);
     const int sorted = p->assume_sorted ? 1 : 0, natural = p->natural ? 1 : 0;
     c->mg_counts[6] = VCFXG_MG_PATH_SORT;
@@ -104,63 +93,47 @@ int vcfxg_merge(vcfxg_ctx *c, const vcfxg_mg_params *p, vcfxg_summary *out) {
     for (int i = 0; i < 6; i++) c->mg_counts[i] = head[1 + i];
     c->mg_counts[7] = head[1 + 7];
     if (nw) {
-        r = ensure(c, c->mg_k0, 8 * nw);
-        if (!r) r = ensure(c, c->mg_k1, 8 * nw);
-        if (!r) r = ensure(c, c->mg_v0, 4 * nw);
-        if (!r) r = ensure(c, c->mg_v1, 4 * nw);
-        if (!r) r = ensure(c, c->mg_len, 8 * (nw + 1));
-        if (!r) r = ensure(c, c->mg_off, 8 * (nw + 1));
-        if (!r) r = ensure(c, c->mg_src, 8 * (nw + 1));
+        SortScratch &S = c->mg_sort;
+        r = sort_begin(c, S, nw);
         if (r) return r;
-        uint64_t *k0 = P<uint64_t>(c->mg_k0), *k1 = P<uint64_t>(c->mg_k1);
-        uint32_t *va = P<uint32_t>(c->mg_v0), *vb = P<uint32_t>(c->mg_v1);
-        HIPCHK(c, vcfxg::launch_mg_scatter(L, written, ord, va, c->stream));
+        HIPCHK(c, vcfxg::launch_mg_scatter(L, written, ord, S.va, c->stream));
         bool walk = false;
         if (sorted) {
-            HIPCHK(c, vcfxg::launch_mg_ordered(M, nw, va, counters, c->stream));
+            HIPCHK(c, vcfxg::launch_mg_ordered(M, nw, S.va, counters, c->stream));
             static thread_local uint64_t unordered;
             HIPCHK(c, hipMemcpyAsync(&unordered, counters + 8, 8, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             walk = unordered != 0;
         }
         if (!walk) {
-            size_t t_sort = 0;
-            HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(nullptr, t_sort, k0, k1, va, vb, (int)nw, 0, 64, c->stream));
-            r = ensure(c, c->mg_tmp, t_sort);
-            if (r) return r;
-            auto pass = [&](int part, uint64_t w, uint32_t shift, int end_bit) -> int {
-                HIPCHK(c, vcfxg::launch_mg_part(M, nw, part, w, shift, va, k0, c->stream));
-                HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(c->mg_tmp.p, t_sort, k0, k1, va, vb, (int)nw, 0, end_bit, c->stream));
-                std::swap(va, vb);
+            auto fill = [&](int part, uint64_t w, uint32_t shift) -> int {
+                HIPCHK(c, vcfxg::launch_mg_part(M, nw, part, w, shift, S.va, S.ka, c->stream));
                 return VCFXG_OK;
             };
-            r = pass(kMgPartPos, 0, 0, 64);
-            if (!r) r = pass(kMgPartLen, 0, 0, mg_bits(longest + 1));
-            const uint64_t W = (longest + 7) / 8;
-            for (uint64_t w = W; !r && w-- > 0;) {
-                // the last word's low bytes are zero padding in every key string: shifted out
-                const uint32_t shift = w == W - 1 && longest % 8 ? (uint32_t)(8 * (8 - longest % 8)) : 0;
-                r = pass(kMgPartWord, w, shift, 64 - (int)shift);
-            }
+            auto pass = [&](int part, int end_bit) -> int {
+                const int rf = fill(part, 0, 0);
+                return rf ? rf : sort_pass(c, S, nw, end_bit);
+            };
+            r = pass(kMgPartPos, 64);
+            if (!r) r = pass(kMgPartLen, bit_width(longest + 1));
+            if (!r) r = sort_string_words(c, S, nw, longest, [&](uint64_t w, uint32_t shift) { return fill(kMgPartWord, w, shift); });
             if (natural) {
-                if (!r) r = pass(kMgPartNum, 0, 0, 64);
-                if (!r) r = pass(kMgPartPrefix, 0, 0, 27);
+                if (!r) r = pass(kMgPartNum, 64);
+                if (!r) r = pass(kMgPartPrefix, 27);
             }
             if (r) return r;
         } else {
             c->mg_counts[6] = VCFXG_MG_PATH_WALK;
             uint64_t *state = P<uint64_t>(c->mg_state);
             HIPCHK(c, hipMemsetAsync(state, 0, 64, c->stream));
-            HIPCHK(c, vcfxg::launch_mg_walk_init(M, ord, va, vb, counters, state, c->stream));
+            HIPCHK(c, vcfxg::launch_mg_walk_init(M, ord, S.va, S.vb, counters, state, c->stream));
             const uint64_t steps = c->mg_walk_steps, launches = std::max<uint64_t>((kept + steps - 1) / steps, 1);
-            for (uint64_t k = 0; k < launches; k++) HIPCHK(c, vcfxg::launch_mg_walk(M, va, vb, steps, state, c->stream));
-            std::swap(va, vb);
+            for (uint64_t k = 0; k < launches; k++) HIPCHK(c, vcfxg::launch_mg_walk(M, S.va, S.vb, steps, state, c->stream));
+            std::swap(S.va, S.vb);
         }
-        c->mg_in_v1 = va == P<uint32_t>(c->mg_v1);
         prof_end(c, "mg_order");
         prof_begin(c, "mg_place");
-        HIPCHK(c, vcfxg::launch_srt_len(0, M.line_end, nw, va, P<uint64_t>(c->mg_len), P<uint64_t>(c->mg_src), c->stream));
-        r = exclusive_scan(c, P<uint64_t>(c->mg_len), P<uint64_t>(c->mg_off), (size_t)nw + 1);
+        r = place_lines(c, c->mg_out, M.line_end, 0, S.va, nw);
         if (r) return r;
         prof_end(c, "mg_place");
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -168,7 +141,6 @@ int vcfxg_merge(vcfxg_ctx *c, const vcfxg_mg_params *p, vcfxg_summary *out) {
         prof_end(c, "mg_order");
     }
     prof_collect(c);
-    c->mg_nw = nw;
     c->mg_done = true;
     if (out) {
         out->n_lines = L;
@@ -181,14 +153,7 @@ int vcfxg_merge(vcfxg_ctx *c, const vcfxg_mg_params *p, vcfxg_summary *out) {
 }
 
 int vcfxg_merge_status(vcfxg_ctx *c, uint64_t first, uint64_t count, uint8_t *status) {
-    if (!c || (!status && count)) return VCFXG_E_ARG;
-    if (!c->indexed || !c->mg_done) return VCFXG_E_STATE;
-    if (first > c->n_lines || count > c->n_lines - first) return VCFXG_E_ARG;
-    if (!count) return VCFXG_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(status, P<uint8_t>(c->status) + first, count, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VCFXG_OK;
+    return c ? fetch_status(c, c->mg_done, first, count, status) : VCFXG_E_ARG;
 }
 
 int vcfxg_merge_counts(const vcfxg_ctx *c, uint64_t counts[8]) {
@@ -211,51 +176,17 @@ int vcfxg_merge_files(vcfxg_ctx *c, uint64_t *first_line, uint64_t *bad) {
 }
 
 int vcfxg_merge_order(vcfxg_ctx *c, uint64_t first, uint64_t count, uint32_t *lines) {
-    if (!c || (!lines && count)) return VCFXG_E_ARG;
-    if (!c->indexed || !c->mg_done) return VCFXG_E_STATE;
-    if (first > c->mg_nw || count > c->mg_nw - first) return VCFXG_E_ARG;
-    if (!count) return VCFXG_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const uint32_t *order = P<uint32_t>(c->mg_in_v1 ? c->mg_v1 : c->mg_v0);
-    HIPCHK(c, hipMemcpyAsync(lines, order + first, 4 * count, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VCFXG_OK;
+    return c ? fetch_order(c, c->mg_done, c->mg_sort.va, c->mg_out.n, first, count, lines) : VCFXG_E_ARG;
 }
 
-// Output lines [first, first + k): as many as fit srt_block bytes, one at least (the offsets are
-// read back once per merge; the cut is a search in them), gathered into the text by the sorter's
-// gather.
+// Output lines [first, first + k): as many as fit srt_block bytes, one at least, gathered into the text.
 int vcfxg_merge_text(vcfxg_ctx *c, uint64_t first, uint64_t *lines_taken, uint64_t *bytes) {
     if (!c) return VCFXG_E_ARG;
     if (lines_taken) *lines_taken = 0;
     if (bytes) *bytes = 0;
     if (!c->indexed || !c->mg_done) return VCFXG_E_STATE;
-    const uint64_t nw = c->mg_nw;
-    if (first > nw) return VCFXG_E_ARG;
-    c->text_bytes = 0;
-    if (first == nw) return VCFXG_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (c->mg_off_host.size() != nw + 1) {
-        c->mg_off_host.resize(nw + 1);
-        HIPCHK(c, hipMemcpyAsync(c->mg_off_host.data(), c->mg_off.p, 8 * (nw + 1), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    const uint64_t *off = c->mg_off_host.data();
-    uint64_t k = (uint64_t)(std::upper_bound(off + first + 1, off + nw + 1, off[first] + c->srt_block) - (off + first + 1));
-    if (!k) k = 1;
-    const uint64_t n = off[first + k] - off[first];
-    int r = ensure(c, c->text, n + 32);
-    if (r) return r;
-    prof_begin(c, "mg_gather");
-    HIPCHK(c, vcfxg::launch_srt_gather(P<char>(c->input), P<uint64_t>(c->mg_off), P<uint64_t>(c->mg_src), first, k, n,
-                                       c->srt_nt, P<char>(c->text), c->stream));
-    prof_end(c, "mg_gather");
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    c->text_bytes = n;
-    if (lines_taken) *lines_taken = k;
-    if (bytes) *bytes = n;
-    return VCFXG_OK;
+    if (first > c->mg_out.n) return VCFXG_E_ARG;
+    return text_block(c, c->mg_out, P<char>(c->input), first, c->mg_out.n, c->srt_block, "mg_gather", lines_taken, bytes);
 }
 
 }  // extern "C"

@@ -21,6 +21,24 @@ struct DevBuf {
     size_t cap = 0;
 };
 
+// The stages the keyed line tools share (vcfxg_api_keyed.hip).  Every tool owns its instances: one
+// tool's results stay readable after another tool ran on the context.
+// A stable radix sort of (64-bit key part, line) pairs, pass after pass: (ka, va) holds the pairs to
+// sort, and after a pass the sorted ones; va is the order so far.
+struct SortScratch {
+    DevBuf k0, k1, v0, v1, tmp;
+    size_t t_sort = 0;
+    uint64_t *ka = nullptr, *kb = nullptr;
+    uint32_t *va = nullptr, *vb = nullptr;
+};
+// n output lines as one text: per line its bytes, their scan (n + 1 offsets; on the host once a text
+// call has fetched them) and its first source byte.
+struct TextOrder {
+    DevBuf len, off, src;
+    std::vector<uint64_t> off_host;
+    uint64_t n = 0;
+};
+
 struct vcfxg_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -127,47 +145,44 @@ struct vcfxg_ctx {
     DevBuf cc_mult, cc_isdata, cc_ord, cc_chrom, cc_small;
     uint64_t cc_totals[4] = {0, 0, 0, 0};
     // VCFX_duplicate_remover: per line the five tab offsets, POS and hash, the wave pass's line
-    // list, the data flags and their scan; the (hash, line) pairs before and after the sort, its
-    // temporary storage; run heads and their scan, pending flags; the last call's counts per
+    // list, the data flags and their scan; the sort of the (hash, line) pairs (its temporary storage
+    // also serves the max scan); run heads and their scan, pending flags; the last call's counts per
     // status and its wave-path lines
-    DevBuf dd_tabs, dd_pos, dd_hash, dd_queue, dd_isdata, dd_ord, dd_k0, dd_k1, dd_v0, dd_v1, dd_tmp, dd_hp, dd_head,
-        dd_left;
+    DevBuf dd_tabs, dd_pos, dd_hash, dd_queue, dd_isdata, dd_ord, dd_hp, dd_head, dd_left;
+    SortScratch dd_sort;
     uint64_t dd_counts[6] = {0, 0, 0, 0, 0, 0};
     bool dd_done = false;  // c->status holds the last vcfxg_dedup's statuses (of this index)
     // VCFX_sorter: per line POS, aux (chromToId or CHROM's length) and CHROM's first word, the wave
-    // pass's line list, the written flags and their scan; the (key, line) pairs of the sort and its
-    // temporary storage; per output line its bytes, their scan and its first input byte; the last
-    // call's counts per status and its wave-path lines, its written lines, which of srt_v0 / srt_v1
-    // holds the order; the offsets on the host (fetched by the first vcfxg_sort_text); text bytes
+    // pass's line list, the written flags and their scan; the sort of the (key, line) pairs
+    // (srt_sort.va: the order); the output lines (srt_out.n of them); the last call's counts per
+    // status and its wave-path lines; text bytes
     // per vcfxg_sort_text call (read when the context opens; tests cut between every pair of lines
     // with 64); VCFXG_SRT_NT: bit 0 non-temporal loads, bit 1 non-temporal stores in the gather (both
     // by default: measured 5 to 12 % faster than neither on the bench shard, DESIGN.md "Sorting")
-    DevBuf srt_pos, srt_aux, srt_w0, srt_queue, srt_written, srt_ord, srt_k0, srt_k1, srt_v0, srt_v1, srt_tmp, srt_len,
-        srt_off, srt_src;
+    DevBuf srt_pos, srt_aux, srt_w0, srt_queue, srt_written, srt_ord;
+    SortScratch srt_sort;
+    TextOrder srt_out;
     uint64_t srt_counts[6] = {0, 0, 0, 0, 0, 0};
-    uint64_t srt_nw = 0;
-    bool srt_done = false, srt_in_v1 = false;
-    std::vector<uint64_t> srt_off_host;
+    bool srt_done = false;
     uint64_t srt_block = getenv("VCFXG_SRT_BLOCK")
                              ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_SRT_BLOCK"), nullptr, 10), 1), 1ull << 36)
                              : 256ull << 20;
     int srt_nt = getenv("VCFXG_SRT_NT") ? atoi(getenv("VCFXG_SRT_NT")) & 3 : 3;
     // VCFX_diff_tool: per line the five tab offsets, the key's length and its scan, ALT's token count,
     // POS and CHROM's natural-order parts, the key's hash, the data flags and their scan, the wave
-    // passes' line list; the key text; the data lines in line order; the (hash, line) pairs of the
-    // sort and its temporary storage, run heads and their scan, each element's class, each class's
-    // first file-2 element, pending flags; the walk's two pointers; the unique flags and their scan,
-    // per unique line its bytes, their scan and its key's place (the gather is the sorter's); the
-    // summary words; the last call's counts, its unique lines in all and of file 1; the offsets on
-    // the host (fetched by the first vcfxg_diff_text); text bytes per vcfxg_diff_text call and steps
-    // per launch of the serial walk (read when the context opens; tests use 64 and 7)
+    // passes' line list; the key text; the data lines in line order; the sort of the (hash, line)
+    // pairs (its temporary storage also serves the max scan), run heads and their scan, each
+    // element's class, each class's first file-2 element, pending flags; the walk's two pointers; the
+    // unique flags and their scan; the unique lines' key texts as output lines (df_out.n of them, file
+    // 1's first: df_nu1); the summary words; the last call's counts; text bytes per vcfxg_diff_text
+    // call and steps per launch of the serial walk (read when the context opens; tests use 64 and 7)
     DevBuf df_tabs, df_klen, df_koff, df_ntok, df_posv, df_natv, df_nsuf, df_hash, df_isdata, df_ord, df_queue, df_ktext,
-        df_line, df_k0, df_k1, df_v0, df_v1, df_tmp, df_hp, df_head, df_rep, df_first2, df_left, df_state, df_uflag, df_uord,
-        df_len, df_off, df_src, df_sum;
+        df_line, df_hp, df_head, df_rep, df_first2, df_left, df_state, df_uflag, df_uord, df_sum;
+    SortScratch df_sort;
+    TextOrder df_out;
     uint64_t df_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t df_nu = 0, df_nu1 = 0;
+    uint64_t df_nu1 = 0;
     bool df_done = false;
-    std::vector<uint64_t> df_off_host;
     uint64_t df_block = getenv("VCFXG_DF_BLOCK")
                             ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_DF_BLOCK"), nullptr, 10), 1), 1ull << 36)
                             : 256ull << 20;
@@ -177,19 +192,17 @@ struct vcfxg_ctx {
     // VCFX_merger: per line its file, POS and the key string's descriptor (first word, start, length;
     // with -n the prefix word and the digit run's value), the wave pass's line list, the written
     // flags and their scan; per file (K + 1 words each) its first byte, first line, first '#' line,
-    // first other line, BAD lines, walk cursor and end; the (key part, line) pairs of the sort and
-    // its temporary storage (mg_v0: the written lines in line order; the walk writes mg_v1); per
-    // output line its bytes, their scan and its first input byte; the walk's output count; the last
-    // call's counts, written lines and files, which of mg_v0 / mg_v1 holds the order; the offsets on
-    // the host (fetched by the first vcfxg_merge_text); steps per launch of the walk (read when the
+    // first other line, BAD lines, walk cursor and end; the sort of the (key part, line) pairs
+    // (mg_sort.va: the order; first the written lines in line order, which the walk reads to write
+    // vb); the output lines (mg_out.n of them); the walk's output count; the last call's counts and
+    // files; steps per launch of the walk (read when the
     // context opens; tests use 7).  The text blocks are bounded by srt_block (VCFXG_SRT_BLOCK).
-    DevBuf mg_file, mg_pos, mg_w0, mg_ks, mg_kl, mg_pn, mg_num, mg_queue, mg_written, mg_ord, mg_fmeta, mg_k0, mg_k1, mg_v0,
-        mg_v1, mg_tmp, mg_len, mg_off, mg_src, mg_state;
+    DevBuf mg_file, mg_pos, mg_w0, mg_ks, mg_kl, mg_pn, mg_num, mg_queue, mg_written, mg_ord, mg_fmeta, mg_state;
+    SortScratch mg_sort;
+    TextOrder mg_out;
     uint64_t mg_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t mg_nw = 0;
     uint32_t mg_files = 0;
-    bool mg_done = false, mg_in_v1 = false;
-    std::vector<uint64_t> mg_off_host;
+    bool mg_done = false;
     uint64_t mg_walk_steps = getenv("VCFXG_MG_WALK_STEPS")
                                  ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_MG_WALK_STEPS"), nullptr, 10), 1), 1ull << 24)
                                  : 1ull << 20;
@@ -338,6 +351,44 @@ int exclusive_scan(vcfxg_ctx *c, const uint32_t *in, uint64_t *out, size_t n);
 int exclusive_scan(vcfxg_ctx *c, const uint64_t *in, uint64_t *out, size_t n);
 void note_schedule(vcfxg_ctx *c, const char *what);
 bool load_hints(vcfxg_ctx *c, const char *h, size_t n);
+
+// ---- vcfxg_api_keyed.hip: the stages the keyed line tools share
+// the bits of x: the sort's end bit for a key part whose largest value is x
+int bit_width(uint64_t x);
+// n pairs: the buffers sized, (ka, va) = (k0, v0), the caller's to fill
+int sort_begin(vcfxg_ctx *c, SortScratch &S, uint64_t n);
+// one stable pass over the bits [0, end_bit) of the keys at ka: sorted pairs at (ka, va) afterwards
+int sort_pass(vcfxg_ctx *c, SortScratch &S, uint64_t n, int end_bit);
+// the passes over a key string of at most `longest` bytes, its 8-byte words from the last to the
+// first: fill(w, shift) writes every pair's word w, shifted right by `shift` bits, to S.ka in the
+// order S.va (0: no error)
+template <class Fill>
+int sort_string_words(vcfxg_ctx *c, SortScratch &S, uint64_t n, uint64_t longest, Fill fill) {
+    const uint64_t W = (longest + 7) / 8;
+    for (uint64_t w = W; w-- > 0;) {
+        // the last word's low bytes are zero padding in every key string: shifted out, so the sort's
+        // bit range starts at 0 (the library's merge path, which takes 1 K to 1 M items, builds its
+        // mask with a shift by begin + bits, undefined when that is 64)
+        const uint32_t shift = w == W - 1 && longest % 8 ? (uint32_t)(8 * (8 - longest % 8)) : 0;
+        int r = fill(w, shift);
+        if (!r) r = sort_pass(c, S, n, 64 - (int)shift);
+        if (r) return r;
+    }
+    return VCFXG_OK;
+}
+// n output lines: T's buffers sized (place_begin; the diff tool then fills len and src itself), and
+// for the indexed lines order[0 .. n) their lengths, source bytes and the scan that places them
+int place_begin(vcfxg_ctx *c, TextOrder &T, uint64_t n);
+int place_lines(vcfxg_ctx *c, TextOrder &T, const uint64_t *line_end, int64_t data_start, const uint32_t *order, uint64_t n);
+// Output lines [first, first + taken) of T, first < hi <= T.n: as many as fit `block` bytes and end
+// before line hi, one at least (the offsets are read back once; the cut is a search in them),
+// gathered from src_text into the context's text under the profile region `region`.
+int text_block(vcfxg_ctx *c, TextOrder &T, const char *src_text, uint64_t first, uint64_t hi, uint64_t block,
+               const char *region, uint64_t *taken, uint64_t *bytes);
+// the statuses of lines [first, first + count) of the index / entries [first, first + count) of an
+// order of n lines, to the host (done: the tool's call has run)
+int fetch_status(vcfxg_ctx *c, bool done, uint64_t first, uint64_t count, uint8_t *status);
+int fetch_order(vcfxg_ctx *c, bool done, const uint32_t *order, uint64_t n, uint64_t first, uint64_t count, uint32_t *lines);
 
 // ---- vcfxg_api_af.hip
 int ensure_dense(vcfxg_ctx *c);

@@ -8,8 +8,8 @@
 //                64-bit hash, one sequential byte loop on 16 B loads.  The sample columns are never
 //                read.  A line whose ALT does not end inside the window, or whose POS is not 1..9
 //                digits from its first byte, is queued for k_dd_key_wave, a wave per line (head_tabs,
-//                POS by the general strtol restatement, CHROM / REF hashed lane-strided, ALT a lane
-//                per token), so any line width passes.
+//                POS by the general strtol restatement, dd_pos over parse_c_integer, CHROM / REF
+//                hashed lane-strided, ALT a lane per token), so any line width passes.
 //   (sort)       (hash & mask, line) of the data lines, compacted in line order, stable radix sort:
 //                inside a run of equal hashes the lines ascend
 //   k_dd_heads / k_dd_verify   run heads, (max scan: every element's run head), then a lane per
@@ -19,7 +19,7 @@
 //                elements of the run kept so far (64 candidates a step): correctness does not
 //                depend on the hash.  A run of n equal lines costs n comparisons.
 //
-// The hash.  byte(b, i) = mix((i << 8 | b) + c0) with i the byte's place in its field or token;
+// The hash (mix64, hash_byte, hash_field: vcfxg_keyed.h).  byte(b, i) = mix((i << 8 | b) + c0) with i the byte's place in its field or token;
 // field(bytes) = mix(sum of byte() ^ (len * c1 + c2)); ALT = the plain sum of field(token) over its
 // tokens (commutative: no token order, no sorting) + mix(token count);
 // key = mix(mix(mix(mix(field(CHROM) + 1) ^ POS * c3) + field(REF)) ^ ALT).  mix = splitmix64's
@@ -31,9 +31,7 @@
 // as often in the other (quadratic in the token count, a lane per comparison: ALT fields that
 // differ only in order are rare and short).
 // Mode: stdin splits ALT at every comma (empty tokens count), file drops empty tokens; POS see dd_pos.
-#include <algorithm>
-
-#include "vcfxg_device.h"
+#include "vcfxg_keyed.h"
 #include "vcfxg_kernels.h"
 
 namespace vcfxg {
@@ -50,27 +48,11 @@ struct DdArgs {
     int stdin_mode;
 };
 
-__device__ __forceinline__ uint64_t dd_mix(uint64_t x) {
-    x ^= x >> 30;
-    x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27;
-    x *= 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    return x;
-}
-__device__ __forceinline__ uint64_t dd_byte(uint32_t b, uint64_t i) { return dd_mix(((i << 8) | b) + 0x9E3779B97F4A7C15ull); }
-__device__ __forceinline__ uint64_t dd_field(uint64_t sum, uint64_t len) {
-    return dd_mix(sum ^ (len * 0xD6E8FEB86659FD93ull + 0xA0761D6478BD642Full));
-}
 __device__ __forceinline__ uint64_t dd_key(uint64_t fc, int32_t pos, uint64_t fr, uint64_t alt, uint64_t ntok) {
-    uint64_t h = dd_mix(fc + 1u);
-    h = dd_mix(h ^ ((uint64_t)(uint32_t)pos * 0xE7037ED1A0B428DBull));
-    h = dd_mix(h + fr);
-    return dd_mix(h ^ (alt + dd_mix(ntok)));
-}
-
-__device__ __forceinline__ int64_t dd_line_start(const DdArgs &A, uint64_t li) {
-    return li ? (int64_t)A.line_end[li - 1] + 1 : A.data_start;
+    uint64_t h = mix64(fc + 1u);
+    h = mix64(h ^ ((uint64_t)(uint32_t)pos * 0xE7037ED1A0B428DBull));
+    h = mix64(h + fr);
+    return mix64(h ^ (alt + mix64(ntok)));
 }
 
 // POS of the field [s, fe).  stdin mode: std::stoi of the field, any exception 0 (:115-119): C
@@ -79,33 +61,11 @@ __device__ __forceinline__ int64_t dd_line_start(const DdArgs &A, uint64_t li) {
 // (bounded here by the input's end), the value saturates at LONG_MAX / LONG_MIN and loses its
 // high 32 bits.
 __device__ __forceinline__ int32_t dd_pos(const char *__restrict__ buf, int64_t s, int64_t fe, int64_t n, int stdin_mode) {
-    const int64_t end = stdin_mode ? fe : n;
-    int64_t p = s;
-    uint32_t b = 0;
-    while (p < end && ((b = byte_at(buf, p)) == ' ' || (b >= 9u && b <= 13u))) p++;
-    bool neg = false;
-    if (p < end && ((b = byte_at(buf, p)) == '-' || b == '+')) {
-        neg = b == '-';
-        p++;
-    }
-    const uint64_t lim = neg ? (1ull << 63) : (1ull << 63) - 1u;
-    uint64_t v = 0;
-    bool any = false, ovf = false;
-    while (p < end && (b = byte_at(buf, p) - '0') <= 9u) {
-        any = true;
-        if (!ovf) {
-            if (v > (lim - b) / 10u) ovf = true;
-            else v = v * 10u + b;
-        }
-        p++;
-    }
-    if (!any) return 0;
-    if (stdin_mode) {
-        if (ovf || v > (neg ? (1ull << 31) : (1ull << 31) - 1u)) return 0;
-        return (int32_t)(uint32_t)(neg ? 0u - v : v);
-    }
-    if (ovf) return neg ? 0 : -1;
-    return (int32_t)(uint32_t)(neg ? 0u - v : v);
+    const CInteger v = parse_c_integer(buf, s, stdin_mode ? fe : n);
+    if (!v.any) return 0;
+    if (stdin_mode) return v.fits_int() ? (int32_t)(uint32_t)v.bits() : 0;
+    if (v.overflow64) return v.neg ? 0 : -1;
+    return (int32_t)(uint32_t)v.bits();
 }
 
 // ---- the key pass ------------------------------------------------------------------------------
@@ -132,18 +92,18 @@ __device__ __forceinline__ bool dd_lane_line(const DdArgs &A, int64_t ls, int64_
             const int64_t p = a + j;
             if (b == '\t') {
                 if (nt == 0) {
-                    fc = dd_field(sum, idx);
+                    fc = hash_field(sum, idx);
                     o.t0 = (uint64_t)p;
                 } else if (nt == 1) {
                     o.t1 = (uint64_t)p;
                 } else if (nt == 2) {
                     o.t2 = (uint64_t)p;
                 } else if (nt == 3) {
-                    fr = dd_field(sum, idx);
+                    fr = hash_field(sum, idx);
                     o.t3 = (uint64_t)p;
                 } else {
                     if (A.stdin_mode || idx) {
-                        asum += dd_field(sum, idx);
+                        asum += hash_field(sum, idx);
                         ntok++;
                     }
                     o.t4 = (uint64_t)p;
@@ -165,13 +125,13 @@ __device__ __forceinline__ bool dd_lane_line(const DdArgs &A, int64_t ls, int64_
                 }
             } else if (nt == 4 && b == ',') {
                 if (A.stdin_mode || idx) {
-                    asum += dd_field(sum, idx);
+                    asum += hash_field(sum, idx);
                     ntok++;
                 }
                 sum = 0;
                 idx = 0;
             } else if (nt != 2) {
-                sum += dd_byte(b, idx);
+                sum += hash_byte(b, idx);
                 idx++;
             }
         }
@@ -183,7 +143,7 @@ __device__ __forceinline__ bool dd_lane_line(const DdArgs &A, int64_t ls, int64_
             return true;
         }
         if (A.stdin_mode || idx) {  // ALT runs to the line's end
-            asum += dd_field(sum, idx);
+            asum += hash_field(sum, idx);
             ntok++;
         }
         o.t4 = (uint64_t)le;
@@ -202,8 +162,8 @@ __device__ __forceinline__ uint64_t dd_wave_sum64(uint64_t x) {
 // field(bytes of [s, e)) by the whole wave
 __device__ __forceinline__ uint64_t dd_wave_field(const char *__restrict__ buf, int64_t s, int64_t e) {
     uint64_t sum = 0;
-    for (int64_t p = s + lane(); p < e; p += kWave) sum += dd_byte(byte_at(buf, p), (uint64_t)(p - s));
-    return dd_field(dd_wave_sum64(sum), (uint64_t)(e - s));
+    for (int64_t p = s + lane(); p < e; p += kWave) sum += hash_byte(byte_at(buf, p), (uint64_t)(p - s));
+    return hash_field(dd_wave_sum64(sum), (uint64_t)(e - s));
 }
 
 // The wave's line [ls, le) (uniform; every lane active): any width.
@@ -230,11 +190,11 @@ __device__ __forceinline__ void dd_wave_line(const DdArgs &A, int64_t ls, int64_
             int64_t q = p;
             uint32_t b;
             while (q < e && (b = byte_at(buf, q)) != ',') {
-                sum += dd_byte(b, (uint64_t)(q - p));
+                sum += hash_byte(b, (uint64_t)(q - p));
                 q++;
             }
             if (A.stdin_mode || q > p) {
-                asum += dd_field(sum, (uint64_t)(q - p));
+                asum += hash_field(sum, (uint64_t)(q - p));
                 ntok++;
             }
         }
@@ -262,7 +222,7 @@ __global__ __launch_bounds__(kDdThreads) void k_dd_key(DdArgs A, uint8_t *__rest
                                                        unsigned long long *__restrict__ counters) {
     const uint64_t nth = gridDim.x * (uint64_t)blockDim.x;
     for (uint64_t li = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; li < A.L; li += nth) {
-        const int64_t ls = dd_line_start(A, li), le = (int64_t)A.line_end[li];
+        const int64_t ls = line_start(A.line_end, A.data_start, li), le = (int64_t)A.line_end[li];
         DdLine o;
         o.t0 = o.t1 = o.t2 = o.t3 = o.t4 = o.hash = 0;
         o.pos = 0;
@@ -288,7 +248,7 @@ __global__ __launch_bounds__(kDdThreads) void k_dd_key_wave(DdArgs A, uint8_t *_
     const uint64_t nw = (gridDim.x * (uint64_t)blockDim.x) / kWave;
     for (uint64_t q = wid; q < nq; q += nw) {
         const uint64_t li = (uint64_t)uniform32((int)queue[q]);
-        const int64_t ls = uniform64(dd_line_start(A, li)), le = uniform64((int64_t)A.line_end[li]);
+        const int64_t ls = uniform64(line_start(A.line_end, A.data_start, li)), le = uniform64((int64_t)A.line_end[li]);
         DdLine o;
         o.t0 = o.t1 = o.t2 = o.t3 = o.t4 = o.hash = 0;
         o.pos = 0;
@@ -354,8 +314,7 @@ __device__ __forceinline__ bool dd_equal(const DdCmp &C, uint32_t x, uint32_t y)
     if (C.pos[x] != C.pos[y]) return false;
     const char *__restrict__ buf = C.buf;
     const uint64_t *tx = C.tabs + 5 * (uint64_t)x, *ty = C.tabs + 5 * (uint64_t)y;
-    const int64_t xs = x ? (int64_t)C.line_end[x - 1] + 1 : C.data_start;
-    const int64_t ys = y ? (int64_t)C.line_end[y - 1] + 1 : C.data_start;
+    const int64_t xs = line_start(C.line_end, C.data_start, x), ys = line_start(C.line_end, C.data_start, y);
     const int64_t cl = (int64_t)tx[0] - xs;
     if (cl != (int64_t)ty[0] - ys || !dd_bytes_equal(buf, xs, ys, cl)) return false;
     const int64_t xr = (int64_t)tx[2] + 1, yr = (int64_t)ty[2] + 1, rl = (int64_t)tx[3] - xr;
@@ -451,29 +410,19 @@ __global__ __launch_bounds__(kDdThreads) void k_dd_count(uint64_t L, const uint8
 #pragma unroll
         for (int i = 0; i < 5; i++) k[i] += st == i ? 1u : 0u;
     }
-#pragma unroll
-    for (int i = 0; i < 5; i++) {
-        const uint32_t t = wave_sum(k[i]);
-        if (lane() == 0 && t) atomicAdd(&red[i], t);
-    }
-    __syncthreads();
-    if (threadIdx.x < 5 && red[threadIdx.x]) atomicAdd(&counters[threadIdx.x], (unsigned long long)red[threadIdx.x]);
+    tally_status(k, red, counters);
 }
 
 // ---- launchers ---------------------------------------------------------------------------------
-
-static unsigned dd_grid(uint64_t items, uint64_t per_block, unsigned max_blocks) {
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((items + per_block - 1) / per_block, max_blocks));
-}
 
 hipError_t launch_dd_key(const char *buf, int64_t data_start, int64_t n, const uint64_t *line_end, uint64_t L,
                          int stdin_mode, uint8_t *status, uint32_t *isdata, uint64_t *tabs, int32_t *pos, uint64_t *hash,
                          uint32_t *queue, unsigned long long *counters, hipStream_t s) {
     if (!L) return hipSuccess;
     const DdArgs A{buf, data_start, n, line_end, L, stdin_mode ? 1 : 0};
-    hipLaunchKernelGGL(k_dd_key, dim3(dd_grid(L, kDdThreads, 8192)), dim3(kDdThreads), 0, s, A, status, isdata, tabs, pos,
+    hipLaunchKernelGGL(k_dd_key, dim3(grid_for(L, kDdThreads, 8192)), dim3(kDdThreads), 0, s, A, status, isdata, tabs, pos,
                        hash, queue, counters);
-    hipLaunchKernelGGL(k_dd_key_wave, dim3(dd_grid(L, kDdWaves, 2048)), dim3(kDdThreads), 0, s, A, status, isdata, tabs, pos,
+    hipLaunchKernelGGL(k_dd_key_wave, dim3(grid_for(L, kDdWaves, 2048)), dim3(kDdThreads), 0, s, A, status, isdata, tabs, pos,
                        hash, queue, counters);
     return hipGetLastError();
 }
@@ -482,14 +431,14 @@ hipError_t launch_dd_gather(uint64_t L, const uint32_t *isdata, const uint64_t *
                             uint32_t hash_bits, uint64_t *keys, uint32_t *vals, hipStream_t s) {
     if (!L) return hipSuccess;
     const uint64_t mask = hash_bits && hash_bits < 64u ? (1ull << hash_bits) - 1u : ~0ull;
-    hipLaunchKernelGGL(k_dd_gather, dim3(dd_grid(L, kDdThreads, 8192)), dim3(kDdThreads), 0, s, L, isdata, ord, hash, mask,
+    hipLaunchKernelGGL(k_dd_gather, dim3(grid_for(L, kDdThreads, 8192)), dim3(kDdThreads), 0, s, L, isdata, ord, hash, mask,
                        keys, vals);
     return hipGetLastError();
 }
 
 hipError_t launch_dd_heads(uint64_t nd, const uint64_t *keys, uint32_t *hp, hipStream_t s) {
     if (!nd) return hipSuccess;
-    hipLaunchKernelGGL(k_dd_heads, dim3((unsigned)((nd + kDdThreads - 1) / kDdThreads)), dim3(kDdThreads), 0, s, nd, keys, hp);
+    hipLaunchKernelGGL(k_dd_heads, flat_grid(nd, kDdThreads), dim3(kDdThreads), 0, s, nd, keys, hp);
     return hipGetLastError();
 }
 
@@ -499,16 +448,16 @@ hipError_t launch_dd_verify(const char *buf, int64_t data_start, const uint64_t 
                             hipStream_t s) {
     if (!nd) return hipSuccess;
     const DdCmp C{buf, line_end, tabs, pos, data_start, stdin_mode ? 1 : 0};
-    hipLaunchKernelGGL(k_dd_verify, dim3((unsigned)((nd + kDdThreads - 1) / kDdThreads)), dim3(kDdThreads), 0, s, C, nd, vals,
+    hipLaunchKernelGGL(k_dd_verify, flat_grid(nd, kDdThreads), dim3(kDdThreads), 0, s, C, nd, vals,
                        head, status, left, counters);
-    hipLaunchKernelGGL(k_dd_resolve, dim3(dd_grid(nd, kDdWaves, 2048)), dim3(kDdThreads), 0, s, C, nd, keys, vals, left,
+    hipLaunchKernelGGL(k_dd_resolve, dim3(grid_for(nd, kDdWaves, 2048)), dim3(kDdThreads), 0, s, C, nd, keys, vals, left,
                        status, counters);
     return hipGetLastError();
 }
 
 hipError_t launch_dd_count(uint64_t L, const uint8_t *status, unsigned long long *counters, hipStream_t s) {
     if (!L) return hipSuccess;
-    hipLaunchKernelGGL(k_dd_count, dim3(dd_grid(L, kDdThreads * 16, 1024)), dim3(kDdThreads), 0, s, L, status, counters);
+    hipLaunchKernelGGL(k_dd_count, dim3(grid_for(L, kDdThreads * 16, 1024)), dim3(kDdThreads), 0, s, L, status, counters);
     return hipGetLastError();
 }
 

@@ -36,14 +36,13 @@
 //                the loop itself, one lane of one wave, a bounded number of steps a launch with the
 //                two pointers kept in device memory; k_df_drain reports what it left.  That is the
 //                slow path of inputs that break the tool's own contract.
-//   k_df_flag / k_df_place  the unique lines' key text spans, in line order, for k_srt_gather.
+//   k_df_flag / k_df_place  the unique lines' key text spans, in line order, for the gather (vcfxg_gather.hip).
 //
 // The hash: sum over the key's bytes of mix((i << 8 | byte) + c0), i the byte's place in the key,
 // then mix(sum ^ (length * c1 + c2)); a sum, so any lane may add any byte.  mix = splitmix64's
-// finaliser.
-#include <algorithm>
-
-#include "vcfxg_device.h"
+// finaliser (mix64, hash_byte, hash_field: vcfxg_keyed.h, with the tab scan window_tabs and the byte
+// order cmp_bytes).
+#include "vcfxg_keyed.h"
 #include "vcfxg_kernels.h"
 
 namespace vcfxg {
@@ -53,23 +52,6 @@ constexpr int kDfWaves = kDfThreads / kWave;
 constexpr uint64_t kDfLaneKey = 96;  // key bytes and ALT tokens a lane writes; more: a wave
 constexpr uint32_t kDfLaneTok = 4;
 constexpr uint32_t kDfPending = 0xFFFFFFFFu;
-
-__device__ __forceinline__ int64_t df_line_start(const DfLines &D, uint64_t li) {
-    return li ? (int64_t)D.line_end[li - 1] + 1 : D.data_start;
-}
-
-__device__ __forceinline__ uint64_t df_mix(uint64_t x) {
-    x ^= x >> 30;
-    x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27;
-    x *= 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    return x;
-}
-__device__ __forceinline__ uint64_t df_byte(uint32_t b, uint64_t i) { return df_mix(((i << 8) | b) + 0x9E3779B97F4A7C15ull); }
-__device__ __forceinline__ uint64_t df_hash(uint64_t sum, uint64_t len) {
-    return df_mix(sum ^ (len * 0xD6E8FEB86659FD93ull + 0xA0761D6478BD642Full));
-}
 
 // ---- the key pass ------------------------------------------------------------------------------
 
@@ -114,22 +96,10 @@ __device__ __forceinline__ void df_lengths(int64_t ls, int natural, const char *
 // The lane's line [ls, le) (not empty, not '#') over its first kDfWindow bytes; false: the wave takes it.
 __device__ __forceinline__ bool df_lane_line(const DfLines &D, int natural, int64_t ls, int64_t le, DfLine &o) {
     const char *__restrict__ buf = D.buf;
-    const int64_t we = le - ls > kDfWindow ? ls + kDfWindow : le;
-    int nt = 0;
-    for (int64_t a = ls & ~(int64_t)15; a < we && nt < 5; a += 16) {
-        uint32_t m = eq_mask16(load16(buf, a), kRepTab) & range_mask16(a, ls, we);
-        while (m && nt < 5) {
-            const uint64_t p = (uint64_t)(a + __builtin_ctz(m));
-            if (nt == 0) o.t0 = p;
-            else if (nt == 1) o.t1 = p;
-            else if (nt == 2) o.t2 = p;
-            else if (nt == 3) o.t3 = p;
-            else o.t4 = p;
-            nt++;
-            m &= m - 1u;
-        }
-    }
-    if (nt < 5 && we < le) return false;  // the window ended before the key fields did
+    int64_t t[5] = {0, 0, 0, 0, 0};
+    const int nt = window_tabs<5>(buf, ls, le, kDfWindow, t);
+    if (nt < 5 && le - ls > kDfWindow) return false;  // the window ended before the key fields did
+    o.t0 = (uint64_t)t[0], o.t1 = (uint64_t)t[1], o.t2 = (uint64_t)t[2], o.t3 = (uint64_t)t[3], o.t4 = (uint64_t)t[4];
     o.st = kDfSkipped;
     if (nt < 4) return true;  // CHROM, POS, ID and REF each end at a tab (:222-251)
     if (nt == 4) o.t4 = (uint64_t)df_line_end(buf, le);
@@ -150,7 +120,7 @@ __device__ __forceinline__ bool df_lane_line(const DfLines &D, int natural, int6
 // The wave's line [ls, le) (uniform; every lane active): any width.
 __device__ __forceinline__ void df_wave_line(const DfLines &D, int natural, int64_t ls, int64_t le, int64_t *lds, DfLine &o) {
     const char *__restrict__ buf = D.buf;
-    int64_t t[5];
+    int64_t t[5] = {0, 0, 0, 0, 0};
     const int nt = head_tabs(buf, ls, le, 5, t, lds);
     o.st = kDfSkipped;
     if (nt < 4) return;
@@ -198,7 +168,7 @@ __global__ void k_df_cut(const uint64_t *__restrict__ line_end, int64_t data_sta
     uint64_t lo = 0, hi = L;  // line li starts at line_end[li - 1] + 1: non-decreasing
     while (lo < hi) {
         const uint64_t mid = lo + (hi - lo) / 2;
-        const uint64_t start = mid ? line_end[mid - 1] + 1u : (uint64_t)data_start;
+        const uint64_t start = (uint64_t)line_start(line_end, data_start, mid);
         if (start >= second_start) hi = mid;
         else lo = mid + 1;
     }
@@ -210,7 +180,7 @@ __global__ __launch_bounds__(kDfThreads) void k_df_key(DfLines D, int natural, u
                                                        unsigned long long *__restrict__ counters) {
     const uint64_t nth = gridDim.x * (uint64_t)blockDim.x;
     for (uint64_t li = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; li < D.L; li += nth) {
-        const int64_t ls = df_line_start(D, li), le = (int64_t)D.line_end[li];
+        const int64_t ls = line_start(D.line_end, D.data_start, li), le = (int64_t)D.line_end[li];
         DfLine o;
         df_clear(o);
         bool have = true;
@@ -236,7 +206,7 @@ __global__ __launch_bounds__(kDfThreads) void k_df_key_wave(DfLines D, int natur
     const uint64_t nw = (gridDim.x * (uint64_t)blockDim.x) / kWave;
     for (uint64_t q = wid; q < nq; q += nw) {
         const uint64_t li = (uint64_t)uniform32((int)queue[q]);
-        const int64_t ls = uniform64(df_line_start(D, li)), le = uniform64((int64_t)D.line_end[li]);
+        const int64_t ls = uniform64(line_start(D.line_end, D.data_start, li)), le = uniform64((int64_t)D.line_end[li]);
         DfLine o;
         df_clear(o);
         df_wave_line(D, natural, ls, le, s_tabs[threadIdx.x / kWave], o);
@@ -249,16 +219,6 @@ __global__ __launch_bounds__(kDfThreads) void k_df_key_wave(DfLines D, int natur
 
 // ---- the key text ------------------------------------------------------------------------------
 
-// the bytes [a, a + an) against [b, b + bn) as unsigned bytes, a prefix before its extensions
-__device__ __forceinline__ int df_cmp_bytes(const char *__restrict__ buf, int64_t a, int64_t an, int64_t b, int64_t bn) {
-    const int64_t n = an < bn ? an : bn;
-    for (int64_t i = 0; i < n; i++) {
-        const uint32_t x = byte_at(buf, a + i), y = byte_at(buf, b + i);
-        if (x != y) return x < y ? -1 : 1;
-    }
-    return an < bn ? -1 : an > bn ? 1 : 0;
-}
-
 // where the token [ts, te) of the ALT field [s, e) stands in ALT': the bytes (each with its ',') of
 // the tokens that sort before it, an equal token when it starts earlier
 __device__ __forceinline__ uint64_t df_token_place(const char *__restrict__ buf, int64_t s, int64_t e, int64_t ts, int64_t te) {
@@ -266,7 +226,7 @@ __device__ __forceinline__ uint64_t df_token_place(const char *__restrict__ buf,
     int64_t a = s;
     for (int64_t p = s; p <= e; p++)
         if (p == e || byte_at(buf, p) == ',') {
-            const int c = df_cmp_bytes(buf, a, p - a, ts, te - ts);
+            const int c = cmp_bytes(buf, a, p - a, ts, te - ts);
             if (c < 0 || (c == 0 && a < ts)) off += (uint64_t)(p - a) + 1u;
             a = p + 1;
         }
@@ -284,12 +244,12 @@ __device__ __forceinline__ uint64_t df_put_token(const char *__restrict__ buf, i
     for (int64_t i = 0; i < te - ts; i++) {
         const uint32_t b = byte_at(buf, ts + i);
         out[off + (uint64_t)i] = (char)b;
-        sum += df_byte(b, k0 + off + (uint64_t)i);
+        sum += hash_byte(b, k0 + off + (uint64_t)i);
     }
     const uint64_t end = off + (uint64_t)(te - ts);
     if (end < (uint64_t)(e - s)) {  // (not ALT''s last token)
         out[end] = ',';
-        sum += df_byte(',', k0 + end);
+        sum += hash_byte(',', k0 + end);
     }
     return sum;
 }
@@ -300,11 +260,11 @@ __device__ __forceinline__ void df_lane_copy(const char *__restrict__ buf, int64
     for (int64_t p = s; p < e; p++) {
         const uint32_t b = byte_at(buf, p);
         out[k] = (char)b;
-        sum += df_byte(b, k++);
+        sum += hash_byte(b, k++);
     }
     if (sep) {
         out[k] = (char)sep;
-        sum += df_byte(sep, k++);
+        sum += hash_byte(sep, k++);
     }
 }
 
@@ -314,13 +274,13 @@ __device__ __forceinline__ void df_wave_copy(const char *__restrict__ buf, int64
     for (int64_t p = s + lane(); p < e; p += kWave) {
         const uint32_t b = byte_at(buf, p);
         out[k + (uint64_t)(p - s)] = (char)b;
-        sum += df_byte(b, k + (uint64_t)(p - s));
+        sum += hash_byte(b, k + (uint64_t)(p - s));
     }
     k += (uint64_t)(e - s);
     if (sep) {
         if (lane() == 0) {
             out[k] = (char)sep;
-            sum += df_byte(sep, k);
+            sum += hash_byte(sep, k);
         }
         k++;
     }
@@ -343,7 +303,7 @@ __global__ __launch_bounds__(kDfThreads) void k_df_text(DfLines D, const uint64_
             continue;
         }
         const uint64_t *t = D.tabs + 5 * li;
-        const int64_t ls = df_line_start(D, li), s = (int64_t)t[3] + 1, e = (int64_t)t[4];
+        const int64_t ls = line_start(D.line_end, D.data_start, li), s = (int64_t)t[3] + 1, e = (int64_t)t[4];
         char *out = ktext + koff[li];
         uint64_t k = 0, sum = 0;
         df_lane_copy(buf, ls, (int64_t)t[0], ':', out, k, sum);
@@ -355,7 +315,7 @@ __global__ __launch_bounds__(kDfThreads) void k_df_text(DfLines D, const uint64_
             for (int64_t p = s; p <= e; p++)
                 if (p == s || byte_at(buf, p - 1) == ',') sum += df_put_token(buf, s, e, p, out + k, k);
         }
-        hash[li] = df_hash(sum, klen);
+        hash[li] = hash_field(sum, klen);
     }
 }
 
@@ -371,7 +331,7 @@ __global__ __launch_bounds__(kDfThreads) void k_df_text_wave(DfLines D, const ui
     for (uint64_t q = wid; q < nq; q += nw) {
         const uint64_t li = (uint64_t)uniform32((int)queue[q]);
         const uint64_t *t = D.tabs + 5 * li;
-        const int64_t ls = uniform64(df_line_start(D, li)), t0 = uniform64((int64_t)t[0]), t1 = uniform64((int64_t)t[1]),
+        const int64_t ls = uniform64(line_start(D.line_end, D.data_start, li)), t0 = uniform64((int64_t)t[0]), t1 = uniform64((int64_t)t[1]),
                       t2 = uniform64((int64_t)t[2]), t3 = uniform64((int64_t)t[3]), e = uniform64((int64_t)t[4]);
         const int64_t s = t3 + 1;
         char *out = ktext + (uint64_t)uniform64((int64_t)koff[li]);
@@ -389,7 +349,7 @@ __global__ __launch_bounds__(kDfThreads) void k_df_text_wave(DfLines D, const ui
             }
         }
         const uint64_t total = (uint64_t)wave_sum<unsigned long long>((unsigned long long)sum);
-        if (lane() == 0) hash[li] = df_hash(total, D.klen[li]);
+        if (lane() == 0) hash[li] = hash_field(total, D.klen[li]);
     }
 }
 
@@ -515,17 +475,17 @@ __device__ __forceinline__ int df_cmp(const DfLines &D, int natural, uint32_t x,
             return 1;
         }
         const int64_t sx = (int64_t)D.nsuf[x], sy = (int64_t)D.nsuf[y];
-        c = df_cmp_bytes(buf, sx, (int64_t)tx[0] - sx, sy, (int64_t)ty[0] - sy);
+        c = cmp_bytes(buf, sx, (int64_t)tx[0] - sx, sy, (int64_t)ty[0] - sy);
     } else {
-        const int64_t xs = df_line_start(D, x), ys = df_line_start(D, y);
-        c = df_cmp_bytes(buf, xs, (int64_t)tx[0] - xs, ys, (int64_t)ty[0] - ys);
+        const int64_t xs = line_start(D.line_end, D.data_start, x), ys = line_start(D.line_end, D.data_start, y);
+        c = cmp_bytes(buf, xs, (int64_t)tx[0] - xs, ys, (int64_t)ty[0] - ys);
     }
     if (c) return c;
     const int64_t px = D.posv[x], py = D.posv[y];
     if (px != py) return px < py ? -1 : 1;
-    c = df_cmp_bytes(buf, (int64_t)tx[2] + 1, (int64_t)(tx[3] - tx[2]) - 1, (int64_t)ty[2] + 1, (int64_t)(ty[3] - ty[2]) - 1);
+    c = cmp_bytes(buf, (int64_t)tx[2] + 1, (int64_t)(tx[3] - tx[2]) - 1, (int64_t)ty[2] + 1, (int64_t)(ty[3] - ty[2]) - 1);
     if (c) return c;
-    return df_cmp_bytes(buf, (int64_t)tx[3] + 1, (int64_t)(tx[4] - tx[3]) - 1, (int64_t)ty[3] + 1, (int64_t)(ty[4] - ty[3]) - 1);
+    return cmp_bytes(buf, (int64_t)tx[3] + 1, (int64_t)(tx[4] - tx[3]) - 1, (int64_t)ty[3] + 1, (int64_t)(ty[4] - ty[3]) - 1);
 }
 
 // counters[8] = 1 when a data line compares greater than the next data line of its file
@@ -637,11 +597,6 @@ __global__ void k_df_sum(uint64_t L, const uint64_t *__restrict__ ord, const uin
 
 // ---- launchers ---------------------------------------------------------------------------------
 
-static unsigned df_grid(uint64_t items, uint64_t per_block, unsigned max_blocks) {
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((items + per_block - 1) / per_block, max_blocks));
-}
-static dim3 df_flat(uint64_t items) { return dim3((unsigned)((items + kDfThreads - 1) / kDfThreads)); }
-
 hipError_t launch_df_cut(const uint64_t *line_end, int64_t data_start, uint64_t L, uint64_t second_start,
                          unsigned long long *counters, hipStream_t s) {
     hipLaunchKernelGGL(k_df_cut, dim3(1), dim3(kWave), 0, s, line_end, data_start, L, second_start, counters);
@@ -650,17 +605,17 @@ hipError_t launch_df_cut(const uint64_t *line_end, int64_t data_start, uint64_t 
 
 hipError_t launch_df_key(const DfLines &D, int natural, uint32_t *queue, unsigned long long *counters, hipStream_t s) {
     if (!D.L) return hipSuccess;
-    hipLaunchKernelGGL(k_df_key, dim3(df_grid(D.L, kDfThreads, 8192)), dim3(kDfThreads), 0, s, D, natural, queue, counters);
-    hipLaunchKernelGGL(k_df_key_wave, dim3(df_grid(D.L, kDfWaves, 2048)), dim3(kDfThreads), 0, s, D, natural, queue, counters);
+    hipLaunchKernelGGL(k_df_key, dim3(grid_for(D.L, kDfThreads, 8192)), dim3(kDfThreads), 0, s, D, natural, queue, counters);
+    hipLaunchKernelGGL(k_df_key_wave, dim3(grid_for(D.L, kDfWaves, 2048)), dim3(kDfThreads), 0, s, D, natural, queue, counters);
     return hipGetLastError();
 }
 
 hipError_t launch_df_text(const DfLines &D, const uint64_t *ord, const uint64_t *koff, char *ktext, uint64_t *hash,
                           uint32_t *line, uint32_t *queue, unsigned long long *counters, hipStream_t s) {
     if (!D.L) return hipSuccess;
-    hipLaunchKernelGGL(k_df_text, dim3(df_grid(D.L, kDfThreads, 8192)), dim3(kDfThreads), 0, s, D, ord, koff, ktext, hash, line,
+    hipLaunchKernelGGL(k_df_text, dim3(grid_for(D.L, kDfThreads, 8192)), dim3(kDfThreads), 0, s, D, ord, koff, ktext, hash, line,
                        queue, counters);
-    hipLaunchKernelGGL(k_df_text_wave, dim3(df_grid(D.L, kDfWaves, 2048)), dim3(kDfThreads), 0, s, D, koff, ktext, hash, queue,
+    hipLaunchKernelGGL(k_df_text_wave, dim3(grid_for(D.L, kDfWaves, 2048)), dim3(kDfThreads), 0, s, D, koff, ktext, hash, queue,
                        counters);
     return hipGetLastError();
 }
@@ -669,7 +624,7 @@ hipError_t launch_df_pairs(uint64_t nd, const uint32_t *line, const uint64_t *ha
                            uint32_t *vals, hipStream_t s) {
     if (!nd) return hipSuccess;
     const uint64_t mask = hash_bits && hash_bits < 64u ? (1ull << hash_bits) - 1u : ~0ull;
-    hipLaunchKernelGGL(k_df_pairs, df_flat(nd), dim3(kDfThreads), 0, s, nd, line, hash, mask, keys, vals);
+    hipLaunchKernelGGL(k_df_pairs, flat_grid(nd, kDfThreads), dim3(kDfThreads), 0, s, nd, line, hash, mask, keys, vals);
     return hipGetLastError();
 }
 
@@ -678,24 +633,24 @@ hipError_t launch_df_classes(const char *ktext, const uint64_t *koff, const uint
                              uint8_t *status, unsigned long long *counters, hipStream_t s) {
     if (!nd) return hipSuccess;
     const DfKeys K{ktext, koff, klen};
-    hipLaunchKernelGGL(k_df_verify, df_flat(nd), dim3(kDfThreads), 0, s, K, nd, vals, head, rep, first2, left, counters);
-    hipLaunchKernelGGL(k_df_resolve, dim3(df_grid(nd, kDfWaves, 2048)), dim3(kDfThreads), 0, s, K, nd, keys, vals, left, rep,
+    hipLaunchKernelGGL(k_df_verify, flat_grid(nd, kDfThreads), dim3(kDfThreads), 0, s, K, nd, vals, head, rep, first2, left, counters);
+    hipLaunchKernelGGL(k_df_resolve, dim3(grid_for(nd, kDfWaves, 2048)), dim3(kDfThreads), 0, s, K, nd, keys, vals, left, rep,
                        counters);
-    hipLaunchKernelGGL(k_df_first2, df_flat(nd), dim3(kDfThreads), 0, s, nd, vals, rep, first2, counters);
-    hipLaunchKernelGGL(k_df_decide, df_flat(nd), dim3(kDfThreads), 0, s, nd, vals, rep, first2, status, counters);
+    hipLaunchKernelGGL(k_df_first2, flat_grid(nd, kDfThreads), dim3(kDfThreads), 0, s, nd, vals, rep, first2, counters);
+    hipLaunchKernelGGL(k_df_decide, flat_grid(nd, kDfThreads), dim3(kDfThreads), 0, s, nd, vals, rep, first2, status, counters);
     return hipGetLastError();
 }
 
 hipError_t launch_df_ordered(const DfLines &D, int natural, const uint32_t *line, uint64_t n1, uint64_t nd,
                              unsigned long long *counters, hipStream_t s) {
     if (nd < 2) return hipSuccess;
-    hipLaunchKernelGGL(k_df_ordered, df_flat(nd), dim3(kDfThreads), 0, s, D, natural, line, n1, nd, counters);
+    hipLaunchKernelGGL(k_df_ordered, flat_grid(nd, kDfThreads), dim3(kDfThreads), 0, s, D, natural, line, n1, nd, counters);
     return hipGetLastError();
 }
 
 hipError_t launch_df_bounds(const DfLines &D, int natural, const uint32_t *line, uint64_t n1, uint64_t nd, hipStream_t s) {
     if (!nd) return hipSuccess;
-    hipLaunchKernelGGL(k_df_bounds, df_flat(nd), dim3(kDfThreads), 0, s, D, natural, line, n1, nd);
+    hipLaunchKernelGGL(k_df_bounds, flat_grid(nd, kDfThreads), dim3(kDfThreads), 0, s, D, natural, line, n1, nd);
     return hipGetLastError();
 }
 
@@ -708,18 +663,18 @@ hipError_t launch_df_walk(const DfLines &D, int natural, const uint32_t *line, u
 hipError_t launch_df_drain(const uint32_t *line, uint64_t n1, uint64_t nd, const uint64_t *state, uint8_t *status,
                            hipStream_t s) {
     if (!nd) return hipSuccess;
-    hipLaunchKernelGGL(k_df_drain, df_flat(nd), dim3(kDfThreads), 0, s, line, n1, nd, state, status);
+    hipLaunchKernelGGL(k_df_drain, flat_grid(nd, kDfThreads), dim3(kDfThreads), 0, s, line, n1, nd, state, status);
     return hipGetLastError();
 }
 
 hipError_t launch_df_flag(uint64_t L, const uint8_t *status, uint32_t *uflag, hipStream_t s) {
-    hipLaunchKernelGGL(k_df_flag, dim3(df_grid(L + 1, kDfThreads * 4, 2048)), dim3(kDfThreads), 0, s, L, status, uflag);
+    hipLaunchKernelGGL(k_df_flag, dim3(grid_for(L + 1, kDfThreads * 4, 2048)), dim3(kDfThreads), 0, s, L, status, uflag);
     return hipGetLastError();
 }
 
 hipError_t launch_df_place(uint64_t L, const uint32_t *uflag, const uint64_t *uord, const uint64_t *koff,
                            const uint64_t *klen, uint64_t *len, uint64_t *src, hipStream_t s) {
-    hipLaunchKernelGGL(k_df_place, dim3(df_grid(L + 1, kDfThreads * 4, 2048)), dim3(kDfThreads), 0, s, L, uflag, uord, koff,
+    hipLaunchKernelGGL(k_df_place, dim3(grid_for(L + 1, kDfThreads * 4, 2048)), dim3(kDfThreads), 0, s, L, uflag, uord, koff,
                        klen, len, src);
     return hipGetLastError();
 }

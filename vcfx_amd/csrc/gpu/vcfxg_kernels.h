@@ -3,9 +3,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "vcfxg_walk_layout.h"
 
 namespace vcfxg {
+
+// launch shapes: blocks of per_block items each, one at least and max_blocks at most (a grid-stride
+// kernel); a block of `threads` for every `threads` items (a kernel of one item per thread)
+inline unsigned grid_for(uint64_t items, uint64_t per_block, unsigned max_blocks) {
+    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((items + per_block - 1) / per_block, max_blocks));
+}
+inline dim3 flat_grid(uint64_t items, unsigned threads) { return dim3((unsigned)((items + threads - 1) / threads)); }
 
 // per-line head summary shared by the AF / GQ head passes (k_line_meta, k_af_combine)
 enum : uint8_t { kMetaEmpty = 0, kMetaGt = 1, kMetaFull = 2, kMetaHeader = 3, kMetaGated = 4 };
@@ -467,11 +476,8 @@ hipError_t launch_fa_transpose(const uint8_t *M, uint64_t pitch, uint64_t ncols,
 // key of every written line at ord[line] (the exclusive scan of written): natural (id, POS) in one
 // word, lexicographic (CHROM length + 1) << 32 | POS; a header line's key is 0, a stdin-mode empty
 // CHROM's length word all ones.  launch_srt_word: keys[j] = word w of the CHROM of line vals[j] (0
-// for a header line, all ones for stdin mode's empty CHROM), shifted right by `shift` bits.  launch_srt_len: len[j] = the bytes
-// of output line j with its '\n', src[j] = its first input byte (len[nw] = 0).  launch_srt_gather:
-// output lines [first, first + k) (off: the scan of len) as bytes [0, off[first + k] - off[first])
-// of text (16 B aligned, 16 spare bytes): aligned 16 B stores only.  nt: bit 0 non-temporal loads,
-// bit 1 non-temporal stores.
+// for a header line, all ones for stdin mode's empty CHROM), shifted right by `shift` bits.  The output
+// lines are placed and gathered by launch_line_len and launch_text_gather (below).
 enum : uint8_t { kSrtEmpty = 0, kSrtKept = 1, kSrtPre = 2, kSrtBad = 3, kSrtHeader = 4 };
 constexpr int kSrtWindow = 64;
 hipError_t launch_srt_key(const char *buf, int64_t data_start, const uint64_t *line_end, uint64_t L, int stdin_mode,
@@ -485,11 +491,6 @@ hipError_t launch_srt_scatter(uint64_t L, int stdin_mode, int natural, const uin
 hipError_t launch_srt_word(const char *buf, int64_t data_start, const uint64_t *line_end, uint64_t nw, int stdin_mode,
                            uint32_t w, uint32_t shift, const uint32_t *vals, const uint8_t *status, const uint32_t *aux,
                            const uint64_t *w0, uint64_t *keys, hipStream_t s);
-hipError_t launch_srt_len(int64_t data_start, const uint64_t *line_end, uint64_t nw, const uint32_t *order,
-                          uint64_t *len, uint64_t *src, hipStream_t s);
-hipError_t launch_srt_gather(const char *buf, const uint64_t *off, const uint64_t *src, uint64_t first, uint64_t k,
-                             uint64_t bytes, int nt, char *text, hipStream_t s);
-
 // VCFX_diff_tool (vcfxg_df.hip) over the L indexed lines of two files in one text; the lines from
 // `cut` on are file 2's (launch_df_cut: counters[7] = the first line that starts at or after
 // second_start).  launch_df_key: per line its status (kDfEmpty / kDfHeader / kDfSkipped, or kDfData:
@@ -509,7 +510,7 @@ hipError_t launch_srt_gather(const char *buf, const uint64_t *off, const uint64_
 // file; launch_df_bounds: each data line's status from three binary searches; launch_df_walk: at
 // most `steps` steps of the two-pointer loop from state[0..1] (one wave); launch_df_drain: the lines
 // the loop left are unique.  launch_df_flag: uflag[line] = 1 for a unique line (uflag[L] = 0);
-// launch_df_place: len / src of every unique line at uord[line] (len[U] = 0) for launch_srt_gather;
+// launch_df_place: len / src of every unique line at uord[line] (len[U] = 0) for launch_text_gather;
 // launch_df_sum: sum[0..7] = vcfxg_diff_counts' words but the path.
 enum : uint8_t { kDfEmpty = 0, kDfCommon = 1, kDfUnique = 2, kDfSkipped = 3, kDfHeader = 4, kDfRepeat = 5, kDfData = 6 };
 constexpr int kDfWindow = 64;
@@ -594,5 +595,15 @@ hipError_t launch_mg_walk_init(const MgLines &M, const uint64_t *ord, const uint
                                const unsigned long long *counters, uint64_t *state, hipStream_t s);
 hipError_t launch_mg_walk(const MgLines &M, const uint32_t *line, uint32_t *out, uint64_t steps, uint64_t *state,
                           hipStream_t s);
+
+// The ordered-text stage of the sorter, the merger and the diff tool (vcfxg_gather.hip).
+// launch_line_len: len[j] = the bytes of output line j = indexed line order[j] with its '\n', src[j] =
+// its first input byte (len[nw] = 0).  launch_text_gather: output lines [first, first + k) (off: the
+// scan of len) as bytes [0, off[first + k] - off[first]) of text (16 B aligned, 16 spare bytes):
+// aligned 16 B stores only.  nt: bit 0 non-temporal loads, bit 1 non-temporal stores.
+hipError_t launch_line_len(int64_t data_start, const uint64_t *line_end, uint64_t nw, const uint32_t *order, uint64_t *len,
+                           uint64_t *src, hipStream_t s);
+hipError_t launch_text_gather(const char *buf, const uint64_t *off, const uint64_t *src, uint64_t first, uint64_t k,
+                              uint64_t bytes, int nt, char *text, hipStream_t s);
 
 }  // namespace vcfxg

@@ -987,12 +987,7 @@ __global__ __launch_bounds__(kFmtWaves *kWave) void k_af_format_w(const char *__
 // =======================================================================================
 // launchers
 // =======================================================================================
-static unsigned grid_for(int64_t n, int64_t per, unsigned cap) {
-    int64_t g = (n + per - 1) / per;
-    if (g < 1) g = 1;
-    return (unsigned)(g > cap ? cap : g);
-}
-
+// (grid_for: vcfxg_kernels.h; every count passed here is non-negative)
 int idx_pos_cap() { return kPosCap; }
 int64_t idx_wchunk_bytes() { return kWChunk; }
 int64_t idx_wchunks(int64_t lo, int64_t hi) {

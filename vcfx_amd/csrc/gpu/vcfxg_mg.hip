@@ -20,7 +20,8 @@
 //   k_mg_class   every '#' line HEADER (written) or DROPPED; the written flag; the status counts,
 //                BAD per file, the longest key string of a kept line.
 //   mg_cmp       the comparator over two lines' descriptors; it reads input bytes only past the
-//                cached word.
+//                cached word (cmp_bytes from byte 8; vcfxg_keyed.h, with line_start, key_word,
+//                window_tabs, parse_c_integer and tally_status).
 //   sort path    k_mg_scatter: the written lines compacted in line order; k_mg_part: one part of the
 //                key per stable LSD pass: POS (sign flipped), the key string's length + 1, its
 //                8-byte words from the last to the first; with -n then the digit run's value and
@@ -31,10 +32,8 @@
 //                files in registers, a butterfly takes the wave-wide least (the lowest file among
 //                equals), the owner appends the line and advances.  A bounded number of steps a
 //                launch; the K cursors and the output count live in device memory between launches.
-//   The gather is the sorter's (launch_srt_len, launch_srt_gather).
-#include <algorithm>
-
-#include "vcfxg_device.h"
+//   The output lines are placed and gathered by vcfxg_gather.hip (launch_line_len, launch_text_gather).
+#include "vcfxg_keyed.h"
 #include "vcfxg_kernels.h"
 
 namespace vcfxg {
@@ -42,10 +41,6 @@ namespace vcfxg {
 constexpr int kMgThreads = 256;
 constexpr int kMgWaves = kMgThreads / kWave;
 constexpr uint32_t kMgNone = 0xFFFFFFFFu;
-
-__device__ __forceinline__ int64_t mg_line_start(const MgLines &M, uint64_t li) {
-    return li ? (int64_t)M.line_end[li - 1] + 1 : 0;
-}
 
 // the file of line li: the last f in [0, K) with first_line[f] <= li (first_line[0] = 0)
 __device__ __forceinline__ uint32_t mg_file_of(const MgLines &M, uint64_t li) {
@@ -65,40 +60,12 @@ struct MgLine {
     uint8_t st;
 };
 
-// std::stol of the field [s, fe) (:87): C white space skipped, one sign, decimal digits, the rest
-// ignored; no digit or a value outside long fails
+// std::stol of the field [s, fe) (:87): C's integer grammar; no digit or a value outside long fails
 __device__ __forceinline__ bool mg_stol(const char *__restrict__ buf, int64_t s, int64_t fe, int64_t &pos) {
-    int64_t p = s;
-    uint32_t b = 0;
-    while (p < fe && ((b = byte_at(buf, p)) == ' ' || (b >= 9u && b <= 13u))) p++;
-    bool neg = false;
-    if (p < fe && ((b = byte_at(buf, p)) == '-' || b == '+')) {
-        neg = b == '-';
-        p++;
-    }
-    const uint64_t lim = neg ? (1ull << 63) : (1ull << 63) - 1u;
-    uint64_t v = 0;
-    bool any = false, ovf = false;
-    while (p < fe && (b = byte_at(buf, p) - '0') <= 9u) {
-        any = true;
-        if (!ovf) {
-            if (v > (lim - b) / 10u) ovf = true;  // v * 10 + b > lim, exactly
-            else v = v * 10u + b;
-        }
-        p++;
-    }
-    if (!any || ovf) return false;
-    pos = (int64_t)(neg ? 0ull - v : v);
+    const CInteger v = parse_c_integer(buf, s, fe);
+    if (!v.any || v.overflow64) return false;
+    pos = (int64_t)v.bits();
     return true;
-}
-
-// the bytes [s, s + len) 's first eight big-endian, zero-padded past the end
-__device__ __forceinline__ uint64_t mg_word(const char *__restrict__ buf, int64_t s, uint64_t len, uint64_t w) {
-    uint64_t x = 0;
-    const uint64_t a = 8u * w;
-#pragma unroll
-    for (int i = 0; i < 8; i++) x = (x << 8) | (a + (uint64_t)i < len ? (uint64_t)byte_at(buf, s + (int64_t)a + i) : 0ull);
-    return x;
 }
 
 // the data line that starts at ls with its first two tabs at t0 and t1
@@ -128,7 +95,7 @@ __device__ __forceinline__ void mg_parse(const char *__restrict__ buf, int natur
     }
     o.ks = (uint64_t)p;
     o.kl = (uint64_t)(t0 - p);
-    o.w0 = mg_word(buf, p, o.kl, 0);
+    o.w0 = key_word(buf, p, (int64_t)o.kl, 0);
 }
 
 __device__ __forceinline__ void mg_clear(MgLine &o) {
@@ -160,7 +127,7 @@ __global__ __launch_bounds__(kMgThreads) void k_mg_cut(MgLines M) {
         uint64_t lo = 0, hi = M.L;  // line li starts at line_end[li - 1] + 1: non-decreasing
         while (lo < hi) {
             const uint64_t mid = lo + (hi - lo) / 2;
-            if ((uint64_t)mg_line_start(M, mid) >= start) hi = mid;
+            if ((uint64_t)line_start(M.line_end, 0, mid) >= start) hi = mid;
             else lo = mid + 1;
         }
         M.first_line[f] = lo;
@@ -183,7 +150,7 @@ __global__ __launch_bounds__(kMgThreads) void k_mg_key(MgLines M, uint32_t *__re
     const char *__restrict__ buf = M.buf;
     const uint64_t nth = gridDim.x * (uint64_t)blockDim.x;
     for (uint64_t li = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; li < M.L; li += nth) {
-        const int64_t ls = mg_line_start(M, li), le = (int64_t)M.line_end[li];
+        const int64_t ls = line_start(M.line_end, 0, li), le = (int64_t)M.line_end[li];
         const uint32_t f = mg_file_of(M, li);
         M.file[li] = f;
         MgLine o;
@@ -194,23 +161,15 @@ __global__ __launch_bounds__(kMgThreads) void k_mg_key(MgLines M, uint32_t *__re
             continue;
         }
         // a file's first line of a class follows the file's start or a line of another class
-        const int prev = li == M.first_line[f] ? 0 : mg_class_of(buf, mg_line_start(M, li - 1), ls - 1);
+        const int prev = li == M.first_line[f] ? 0 : mg_class_of(buf, line_start(M.line_end, 0, li - 1), ls - 1);
         if (prev != cls) atomicMin((unsigned long long *)(cls == 1 ? M.first_hash : M.first_data) + f, (unsigned long long)li);
         if (cls == 1) {
             M.status[li] = kMgHeader;  // (k_mg_class decides: written or dropped)
             continue;
         }
-        const int64_t we = le - ls > kMgWindow ? ls + kMgWindow : le;
         int64_t t[2] = {-1, -1};
-        int nt = 0;
-        for (int64_t a = ls & ~(int64_t)15; a < we && nt < 2; a += 16) {
-            uint32_t m = eq_mask16(load16(buf, a), kRepTab) & range_mask16(a, ls, we);
-            while (m && nt < 2) {
-                t[nt++] = a + __builtin_ctz(m);
-                m &= m - 1u;
-            }
-        }
-        if (nt < 2 && we < le) {  // the window ended before the key fields did
+        const int nt = window_tabs<2>(buf, ls, le, kMgWindow, t);
+        if (nt < 2 && le - ls > kMgWindow) {  // the window ended before the key fields did
             queue[atomicAdd(&counters[5], 1ull)] = (uint32_t)li;
             continue;
         }
@@ -230,7 +189,7 @@ __global__ __launch_bounds__(kMgThreads) void k_mg_key_wave(MgLines M, const uin
     const uint64_t nw = (gridDim.x * (uint64_t)blockDim.x) / kWave;
     for (uint64_t q = wid; q < nq; q += nw) {
         const uint64_t li = (uint64_t)uniform32((int)queue[q]);
-        const int64_t ls = uniform64(mg_line_start(M, li)), le = uniform64((int64_t)M.line_end[li]);
+        const int64_t ls = uniform64(line_start(M.line_end, 0, li)), le = uniform64((int64_t)M.line_end[li]);
         int64_t t[2] = {-1, -1};
         const int nt = head_tabs(M.buf, ls, le, 2, t, s_tabs[threadIdx.x / kWave]);
         MgLine o;
@@ -280,14 +239,8 @@ __global__ __launch_bounds__(kMgThreads) void k_mg_class(MgLines M, uint32_t *__
 #pragma unroll
         for (int i = 0; i < 5; i++) k[i] += st == i ? 1u : 0u;
     }
-#pragma unroll
-    for (int i = 0; i < 5; i++) {
-        const uint32_t t = wave_sum(k[i]);
-        if (lane() == 0 && t) atomicAdd(&red[i], t);
-    }
     if (longest) atomicMax(&longest_s, (unsigned long long)longest);
-    __syncthreads();
-    if (threadIdx.x < 5 && red[threadIdx.x]) atomicAdd(&counters[threadIdx.x], (unsigned long long)red[threadIdx.x]);
+    tally_status(k, red, counters);
     if (threadIdx.x == 5 && longest_s) atomicMax(&counters[6], longest_s);
 }
 
@@ -319,12 +272,8 @@ __device__ __forceinline__ int mg_cmp(const char *__restrict__ buf, const MgHead
     if (a.pn != b.pn) return a.pn < b.pn ? -1 : 1;
     if (a.num != b.num) return a.num < b.num ? -1 : 1;
     if (a.w0 != b.w0) return a.w0 < b.w0 ? -1 : 1;
-    const uint64_t n = a.kl < b.kl ? a.kl : b.kl;
-    for (uint64_t i = 8; i < n; i++) {
-        const uint32_t x = byte_at(buf, (int64_t)(a.ks + i)), y = byte_at(buf, (int64_t)(b.ks + i));
-        if (x != y) return x < y ? -1 : 1;
-    }
-    if (a.kl != b.kl) return a.kl < b.kl ? -1 : 1;
+    const int c = cmp_bytes(buf, (int64_t)a.ks, (int64_t)a.kl, (int64_t)b.ks, (int64_t)b.kl, 8);
+    if (c) return c;
     return a.pos < b.pos ? -1 : a.pos > b.pos ? 1 : 0;
 }
 
@@ -363,7 +312,7 @@ __global__ __launch_bounds__(kMgThreads) void k_mg_part(MgLines M, uint64_t nw, 
         else if (part == kMgPartNum) key = M.num[li];
         else if (part == kMgPartPrefix) key = (uint64_t)M.pn[li] + 1u;
         else if (w == 0) key = M.w0[li] >> shift;
-        else if (8u * w < M.kl[li]) key = mg_word(M.buf, (int64_t)M.ks[li], M.kl[li], w) >> shift;
+        else if (8u * w < M.kl[li]) key = key_word(M.buf, (int64_t)M.ks[li], (int64_t)M.kl[li], w) >> shift;
     }
     keys[j] = key;
 }
@@ -457,53 +406,48 @@ __global__ __launch_bounds__(kWave) void k_mg_walk(MgLines M, const uint32_t *__
 
 // ---- launchers ---------------------------------------------------------------------------------
 
-static unsigned mg_grid(uint64_t items, uint64_t per_block, unsigned max_blocks) {
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((items + per_block - 1) / per_block, max_blocks));
-}
-static dim3 mg_flat(uint64_t items) { return dim3((unsigned)((items + kMgThreads - 1) / kMgThreads)); }
-
 hipError_t launch_mg_cut(const MgLines &M, hipStream_t s) {
-    hipLaunchKernelGGL(k_mg_cut, dim3(mg_grid((uint64_t)M.K + 1, kMgThreads, 1024)), dim3(kMgThreads), 0, s, M);
+    hipLaunchKernelGGL(k_mg_cut, dim3(grid_for((uint64_t)M.K + 1, kMgThreads, 1024)), dim3(kMgThreads), 0, s, M);
     return hipGetLastError();
 }
 
 hipError_t launch_mg_key(const MgLines &M, uint32_t *queue, unsigned long long *counters, hipStream_t s) {
     if (!M.L) return hipSuccess;
-    hipLaunchKernelGGL(k_mg_key, dim3(mg_grid(M.L, kMgThreads, 8192)), dim3(kMgThreads), 0, s, M, queue, counters);
-    hipLaunchKernelGGL(k_mg_key_wave, dim3(mg_grid(M.L, kMgWaves, 2048)), dim3(kMgThreads), 0, s, M, queue, counters);
+    hipLaunchKernelGGL(k_mg_key, dim3(grid_for(M.L, kMgThreads, 8192)), dim3(kMgThreads), 0, s, M, queue, counters);
+    hipLaunchKernelGGL(k_mg_key_wave, dim3(grid_for(M.L, kMgWaves, 2048)), dim3(kMgThreads), 0, s, M, queue, counters);
     return hipGetLastError();
 }
 
 hipError_t launch_mg_class(const MgLines &M, uint32_t *written, unsigned long long *counters, hipStream_t s) {
     if (!M.L) return hipSuccess;
     hipLaunchKernelGGL(k_mg_hdr, dim3(1), dim3(kWave), 0, s, M, counters);
-    hipLaunchKernelGGL(k_mg_class, dim3(mg_grid(M.L, kMgThreads * 4, 1024)), dim3(kMgThreads), 0, s, M, written, counters);
+    hipLaunchKernelGGL(k_mg_class, dim3(grid_for(M.L, kMgThreads * 4, 1024)), dim3(kMgThreads), 0, s, M, written, counters);
     return hipGetLastError();
 }
 
 hipError_t launch_mg_scatter(uint64_t L, const uint32_t *written, const uint64_t *ord, uint32_t *vals, hipStream_t s) {
     if (!L) return hipSuccess;
-    hipLaunchKernelGGL(k_mg_scatter, dim3(mg_grid(L, kMgThreads, 8192)), dim3(kMgThreads), 0, s, L, written, ord, vals);
+    hipLaunchKernelGGL(k_mg_scatter, dim3(grid_for(L, kMgThreads, 8192)), dim3(kMgThreads), 0, s, L, written, ord, vals);
     return hipGetLastError();
 }
 
 hipError_t launch_mg_part(const MgLines &M, uint64_t nw, int part, uint64_t w, uint32_t shift, const uint32_t *vals,
                           uint64_t *keys, hipStream_t s) {
     if (!nw) return hipSuccess;
-    hipLaunchKernelGGL(k_mg_part, mg_flat(nw), dim3(kMgThreads), 0, s, M, nw, part, w, shift, vals, keys);
+    hipLaunchKernelGGL(k_mg_part, flat_grid(nw, kMgThreads), dim3(kMgThreads), 0, s, M, nw, part, w, shift, vals, keys);
     return hipGetLastError();
 }
 
 hipError_t launch_mg_ordered(const MgLines &M, uint64_t nw, const uint32_t *line, unsigned long long *counters,
                              hipStream_t s) {
     if (nw < 2) return hipSuccess;
-    hipLaunchKernelGGL(k_mg_ordered, mg_flat(nw), dim3(kMgThreads), 0, s, M, nw, line, counters);
+    hipLaunchKernelGGL(k_mg_ordered, flat_grid(nw, kMgThreads), dim3(kMgThreads), 0, s, M, nw, line, counters);
     return hipGetLastError();
 }
 
 hipError_t launch_mg_walk_init(const MgLines &M, const uint64_t *ord, const uint32_t *line, uint32_t *out,
                                const unsigned long long *counters, uint64_t *state, hipStream_t s) {
-    hipLaunchKernelGGL(k_mg_walk_init, dim3(mg_grid(M.K, kMgThreads, 1024)), dim3(kMgThreads), 0, s, M, ord, line, out,
+    hipLaunchKernelGGL(k_mg_walk_init, dim3(grid_for(M.K, kMgThreads, 1024)), dim3(kMgThreads), 0, s, M, ord, line, out,
                        counters, state);
     return hipGetLastError();
 }

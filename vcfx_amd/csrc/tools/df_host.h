@@ -1,6 +1,6 @@
 // df_host.h -- the host side of VCFX_diff_tool that needs no device: how the two files become the
 // one text the device indexes (file 1, one '\n' when file 1 is not empty and lacks a final one, file
-// 2), and the walk over one side's text blocks.  Plain C++: tests/host_df_test.cpp builds it under
+// 2).  Plain C++: tests/host_df_test.cpp builds it under
 // ASan + UBSan without a device.
 #pragma once
 #include <stddef.h>
@@ -32,20 +32,5 @@ struct DfJoin {
         total = second_start + n2;
     }
 };
-
-// One side's keys, block after block: text(first, &taken, &bytes) makes the block that begins at
-// key `first` (false: a failed, reported call), write(bytes) writes it out.  A block of no key, or
-// of more keys than are left, ends the walk as a failure: it could not end otherwise.
-template <class Text, class Write>
-bool df_walk_side(uint64_t keys, Text text, Write write) {
-    for (uint64_t first = 0; first < keys;) {
-        uint64_t taken = 0, bytes = 0;
-        if (!text(first, &taken, &bytes)) return false;
-        if (!taken || taken > keys - first) return false;
-        if (!write(bytes)) return false;
-        first += taken;
-    }
-    return true;
-}
 
 }  // namespace vcfxh

@@ -55,19 +55,4 @@ inline void mg_split(const std::string &value, std::vector<std::string> &names) 
     names.emplace_back(value, a);
 }
 
-// The output's lines, block after block: text(first, &taken, &bytes) makes the block that begins
-// at output line `first` (false: a failed, reported call), write(bytes) writes it out.  A block of
-// no line, or of more lines than are left, ends the walk as a failure: it could not end otherwise.
-template <class Text, class Write>
-bool mg_walk_blocks(uint64_t lines, Text text, Write write) {
-    for (uint64_t first = 0; first < lines;) {
-        uint64_t taken = 0, bytes = 0;
-        if (!text(first, &taken, &bytes)) return false;
-        if (!taken || taken > lines - first) return false;
-        if (!write(bytes)) return false;
-        first += taken;
-    }
-    return true;
-}
-
 }  // namespace vcfxh

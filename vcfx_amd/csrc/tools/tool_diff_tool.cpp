@@ -91,7 +91,7 @@ bool run(const Input &a, const Input &b, const std::string &path1, const std::st
     }
     for (int side = 0; side < 2; side++) {
         header(out, side ? "\nVariants unique to " : "Variants unique to ", side ? path2 : path1);
-        const bool ok = df_walk_side(
+        const bool ok = write_text_blocks(
             unique[side],
             [&](uint64_t first, uint64_t *taken, uint64_t *bytes) {
                 return gpu_ok(g, vcfxg_diff_text(g, side, first, taken, bytes), "diff_text", err.fd);

@@ -90,7 +90,7 @@ bool run(std::vector<File> &files, bool sorted, bool natural, Out &out, Out &err
         vcfxg_summary s;
         if (!gpu_ok(g, vcfxg_merge(g, &P, &s), "merge", err.fd)) return false;
         phase("merge");
-        const bool ok = mg_walk_blocks(
+        const bool ok = write_text_blocks(
             s.rows,
             [&](uint64_t first, uint64_t *taken, uint64_t *bytes) {
                 return gpu_ok(g, vcfxg_merge_text(g, first, taken, bytes), "merge_text", err.fd);

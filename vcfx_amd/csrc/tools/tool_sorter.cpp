@@ -75,12 +75,13 @@ bool run(const Input &in, bool stdin_mode, bool natural, Out &out, Out &err) {
     vcfxg_summary s;
     if (!gpu_ok(g, vcfxg_sort(g, stdin_mode ? VCFXG_MODE_STDIN : VCFXG_MODE_FILE, &P, &s), "sort", err.fd)) return false;
     phase("sort");
-    for (uint64_t j = 0; j < s.rows;) {
-        uint64_t k = 0, bytes = 0;
-        if (!gpu_ok(g, vcfxg_sort_text(g, j, &k, &bytes), "sort_text", err.fd)) return false;
-        if (!write_device_text(g, bytes, out, err.fd)) return false;
-        j += k;
-    }
+    const bool ok = write_text_blocks(
+        s.rows,
+        [&](uint64_t first, uint64_t *taken, uint64_t *bytes) {
+            return gpu_ok(g, vcfxg_sort_text(g, first, taken, bytes), "sort_text", err.fd);
+        },
+        [&](uint64_t bytes) { return write_device_text(g, bytes, out, err.fd); });
+    if (!ok) return false;
     phase("lines written");
     if (s.warn_lines) {
         std::vector<uint8_t> st;

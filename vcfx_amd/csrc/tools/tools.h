@@ -68,4 +68,20 @@ struct GetoptStderr {
     }
     ~GetoptStderr() { done(); }
 };
+
+// A device text of `rows` lines written out block after block (VCFX_sorter, VCFX_merger, a side of
+// VCFX_diff_tool): take(first, &taken, &bytes) makes the block that begins at line `first` (false: a
+// failed, reported call), write(bytes) writes it out.  A block of no line, or of more lines than are
+// left, ends the loop as a failure: it could not end otherwise.
+template <class Take, class Write>
+bool write_text_blocks(uint64_t rows, Take take, Write write) {
+    for (uint64_t first = 0; first < rows;) {
+        uint64_t taken = 0, bytes = 0;
+        if (!take(first, &taken, &bytes)) return false;
+        if (!taken || taken > rows - first) return false;
+        if (!write(bytes)) return false;
+        first += taken;
+    }
+    return true;
+}
 }  // namespace vcfxh
