@@ -789,6 +789,63 @@ int vcfxg_merge_files(vcfxg_ctx *ctx, uint64_t *first_line, uint64_t *bad);
 int vcfxg_merge_order(vcfxg_ctx *ctx, uint64_t first, uint64_t count, uint32_t *lines);
 int vcfxg_merge_text(vcfxg_ctx *ctx, uint64_t first_out_line, uint64_t *lines_taken, uint64_t *bytes);
 
+/* ---- VCFX_region_subsampler (the first join against a side table: is the record inside a BED) ---
+ * The table (vcfxg_regions_load): n_chrom distinct names (their bytes in `names`, name i =
+ * [name_off[i], name_off[i + 1])) and n intervals (chrom_id, 1-based start1 >= 1, end >= start1),
+ * what loadRegions keeps of a BED (VCFX_region_subsampler.cpp:344-381; the host parses the text).
+ * The device sorts the intervals by (name id, start), scans the furthest end along each name (the
+ * "reach") and keeps per name its range; the merged intervals the reference builds
+ * (sortAndMergeIntervals :383-404: joined when start <= last end + 1) are exported in (name id,
+ * start) order by vcfxg_regions_merged (*n = their number; more than cap: nothing is copied and the
+ * caller repeats the call with room for all).  The names go into an open-addressing dictionary over
+ * their hash; hash_bits masks the hash; every hit is confirmed byte by byte, so no answer depends
+ * on the hash.  A table of zero intervals is legal; n < 2^31.  The table stays resident across
+ * loads and indexes of the input until the next vcfxg_regions_load.
+ * vcfxg_region_filter over the indexed lines (vcfxg_index, from offset 0 for the tool).  Lines end at
+ * '\n' only; a '\r' is a byte of its line.  Per line status (vcfxg_region_status), the checks in
+ * this order:
+ *   VCFXG_RS_EMPTY   an empty line: "\n" written (:451-455, :528-531)
+ *   VCFXG_RS_HEADER  a line that starts with '#', wherever it stands: written (:458-466, :532-538)
+ *   VCFXG_RS_EARLY   a data line before the first line that starts with "#CHROM": dropped, "Warning:
+ *                    data line encountered before #CHROM => skipping." (:469-475, :539-542)
+ *   VCFXG_RS_SHORT   VCFXG_MODE_FILE: CHROM or POS missing or empty, "Warning: line has insufficient
+ *                    columns => skipping." (:478-487); VCFXG_MODE_STDIN: fewer than seven tabs,
+ *                    "Warning: line has <8 columns => skipping." (:544-548)
+ *   VCFXG_RS_BADPOS  VCFXG_MODE_STDIN only: std::stoi of POS throws (no digits after the white space
+ *                    and one sign, or a value outside int), "Warning: invalid POS => skipping."
+ *                    (:552-558)
+ *   VCFXG_RS_IN      CHROM's bytes equal a name and POS lies in one of its intervals: written
+ *   VCFXG_RS_OUT     every other data line: dropped silently
+ * VCFXG_MODE_FILE reads POS as parseIntFast does (:190-198): every digit byte of the field, the other
+ * bytes skipped, accumulated modulo 2^32 and cast to int ("1e1" is 11, "-5" is 5, "abc" is 0,
+ * "4294967301" is 5); eight columns are not needed.  VCFXG_MODE_STDIN reads it with std::stoi.
+ * Outside the domain: an input with NUL bytes, a BED end or start of 2147483647.
+ * A line whose first two (stdin mode: seven) tabs lie within its first VCFXG_RS_WINDOW bytes, or that
+ * is no longer than that, is parsed by one lane; every other line by a wave (general_records counts
+ * those).  rows = IN lines, warn_lines = EARLY + SHORT + BADPOS lines, data_lines = the lines that
+ * are neither empty nor '#' lines, n_lines.  vcfxg_region_counts: the lines per status
+ * (counts[VCFXG_RS_EMPTY .. VCFXG_RS_BADPOS]) and, in counts[7], the lines the wave path parsed.
+ * vcfxg_region_filter without a table and vcfxg_region_status without a filter on this index (and
+ * this table) return VCFXG_E_STATE. */
+#define VCFXG_RS_EMPTY 0
+#define VCFXG_RS_HEADER 1
+#define VCFXG_RS_IN 2
+#define VCFXG_RS_OUT 3
+#define VCFXG_RS_EARLY 4
+#define VCFXG_RS_SHORT 5
+#define VCFXG_RS_BADPOS 6
+#define VCFXG_RS_WINDOW 64
+typedef struct {
+    uint32_t hash_bits; /* 0: all 64 bits; 1..63: only the low bits (tests force collisions) */
+} vcfxg_rs_params;
+int vcfxg_regions_load(vcfxg_ctx *ctx, const char *names, const uint64_t *name_off, uint32_t n_chrom,
+                       const uint32_t *chrom_id, const int32_t *start1, const int32_t *end, uint64_t n,
+                       const vcfxg_rs_params *params);
+int vcfxg_regions_merged(vcfxg_ctx *ctx, uint32_t *chrom_id, int32_t *start1, int32_t *end, uint64_t cap, uint64_t *n);
+int vcfxg_region_filter(vcfxg_ctx *ctx, int mode, vcfxg_summary *out);
+int vcfxg_region_status(vcfxg_ctx *ctx, uint64_t first, uint64_t count, uint8_t *status);
+int vcfxg_region_counts(const vcfxg_ctx *ctx, uint64_t counts[8]);
+
 /* ---- VCFX_haplotype_phaser (LD reuse in block phasing) ------------------
  * Over the lines from data_start (the byte after the '#CHROM' line): per line status 1 variant,
  * 4 '#' line, 3 "<10 fields", 7 invalid POS, 8 no GT in FORMAT, 0 empty (mode VCFXG_MODE_FILE:

@@ -206,6 +206,19 @@ struct vcfxg_ctx {
     uint64_t mg_walk_steps = getenv("VCFXG_MG_WALK_STEPS")
                                  ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_MG_WALK_STEPS"), nullptr, 10), 1), 1ull << 24)
                                  : 1ull << 20;
+    // VCFX_region_subsampler: the table of the last vcfxg_regions_load (it outlives loads and indexes of
+    // the input): its descriptor (RsTableArgs), the names' bytes and offsets, the dictionary, the uploaded intervals (ids, starts,
+    // ends: 3 n words), their sort, the sorted ids and starts, the scan keys and tile maxima, the reach,
+    // per name its range, the open flags and their scan, the merged rows (rs_nm of them); the class
+    // pass's wave list; the last filter's counts per status and its wave-path lines
+    DevBuf rs_tab, rs_names, rs_noff, rs_dict, rs_in, rs_sid, rs_start, rs_key, rs_tile, rs_reach, rs_first, rs_last, rs_open,
+        rs_ord, rs_mid, rs_mstart, rs_mend, rs_queue;
+    SortScratch rs_sort;
+    uint64_t rs_n = 0, rs_nm = 0;
+    uint32_t rs_nchrom = 0;
+    uint64_t rs_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool rs_loaded = false;  // a table is resident
+    bool rs_done = false;    // c->status holds the last vcfxg_region_filter's statuses (of this index)
     // VCFX_multiallelic_splitter: the table; per line of the block its tab offsets, cost and the
     // scans of nAlts and cost; each line's text offset; {lines taken, rows}; the last call's block;
     // lines and text bytes per call (read when the context opens; tests make blocks of one line)

@@ -596,6 +596,43 @@ hipError_t launch_mg_walk_init(const MgLines &M, const uint64_t *ord, const uint
 hipError_t launch_mg_walk(const MgLines &M, const uint32_t *line, uint32_t *out, uint64_t steps, uint64_t *state,
                           hipStream_t s);
 
+// VCFX_region_subsampler (vcfxg_rs.hip).  The table of n intervals (name id, 1-based start, end) over
+// n_chrom names: launch_rs_keys (id << 32 | start, interval) pairs for the stable sort; after it
+// launch_rs_table: the sorted ids and starts, reach[j] = the furthest end among the intervals of j's
+// name up to j (the running maximum of id << 32 | end: scan_key n entries, tile_max rs_scan_tiles(n)),
+// per name its [first, last) in the table (n_chrom entries each, zeroed beforehand), open[j] = 1 where
+// a merged interval begins (n + 1 entries, open[n] zeroed beforehand); launch_rs_rows: the merged
+// intervals at ord (the exclusive scan of open); launch_rs_dict: name id + 1 into dict (dict_mask + 1
+// zeroed slots, at most half of them taken) at its hash masked to hash_bits (1..63), linear probing.
+// launch_rs_class over the L indexed lines against the table (an RsTableArgs in device memory: the
+// kernels load its fields where they use them): per line its status (kRs*); a lane per line over its first
+// kRsWindow bytes, then a wave per line that pass does not settle (queue: L entries; counters[7], zeroed
+// beforehand, counts them); counters[8] (L beforehand) = the first line that starts with "#CHROM", the
+// data lines before it kRsEarly; counters[0..6] += the lines of each status.
+enum : uint8_t { kRsEmpty = 0, kRsHeader = 1, kRsIn = 2, kRsOut = 3, kRsEarly = 4, kRsShort = 5, kRsBadPos = 6 };
+constexpr int kRsWindow = 64;
+struct RsTableArgs {
+    const char *names;
+    const uint64_t *name_off;
+    const uint32_t *dict, *first, *last;
+    const int32_t *start, *reach;
+    uint32_t dict_mask;
+    uint64_t hash_mask;
+};
+inline uint64_t rs_hash_mask(uint32_t hash_bits) { return hash_bits && hash_bits < 64u ? (1ull << hash_bits) - 1u : ~0ull; }
+uint64_t rs_scan_tiles(uint64_t n);
+hipError_t launch_rs_keys(uint64_t n, const uint32_t *id, const int32_t *start, uint64_t *keys, uint32_t *vals, hipStream_t s);
+hipError_t launch_rs_table(uint64_t n, const uint64_t *keys, const uint32_t *vals, const int32_t *end, uint32_t *sid,
+                           int32_t *sstart, uint64_t *scan_key, uint64_t *tile_max, int32_t *reach, uint32_t *first,
+                           uint32_t *last, uint32_t *open, hipStream_t s);
+hipError_t launch_rs_rows(uint64_t n, const uint32_t *sid, const int32_t *sstart, const int32_t *reach, const uint32_t *open,
+                          const uint64_t *ord, uint32_t *m_id, int32_t *m_start, int32_t *m_end, hipStream_t s);
+hipError_t launch_rs_dict(uint32_t n_chrom, const char *names, const uint64_t *name_off, uint32_t hash_bits,
+                          uint32_t dict_mask, uint32_t *dict, hipStream_t s);
+hipError_t launch_rs_class(const char *buf, int64_t data_start, const uint64_t *line_end, uint64_t L, int stdin_mode,
+                           const RsTableArgs *table, uint8_t *status, uint32_t *queue, unsigned long long *counters,
+                           hipStream_t s);
+
 // The ordered-text stage of the sorter, the merger and the diff tool (vcfxg_gather.hip).
 // launch_line_len: len[j] = the bytes of output line j = indexed line order[j] with its '\n', src[j] =
 // its first input byte (len[nw] = 0).  launch_text_gather: output lines [first, first + k) (off: the

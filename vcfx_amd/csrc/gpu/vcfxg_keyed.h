@@ -33,6 +33,18 @@ __device__ __forceinline__ int cmp_bytes(const char *__restrict__ buf, int64_t a
     return an < bn ? -1 : an > bn ? 1 : 0;
 }
 
+// ... and the bytes [a, a + an) of one buffer against [b, b + bn) of another (a line's field against
+// a side table's name)
+__device__ __forceinline__ int cmp_bytes(const char *__restrict__ abuf, int64_t a, int64_t an, const char *__restrict__ bbuf,
+                                         int64_t b, int64_t bn) {
+    const int64_t n = an < bn ? an : bn;
+    for (int64_t i = 0; i < n; i++) {
+        const uint32_t x = byte_at(abuf, a + i), y = byte_at(bbuf, b + i);
+        if (x != y) return x < y ? -1 : 1;
+    }
+    return an < bn ? -1 : an > bn ? 1 : 0;
+}
+
 // The key hashes: a byte's term is mix64((i << 8 | b) + c0), i its place in its field, token or key;
 // a field of `len` bytes with the sum of its terms closes as mix64(sum ^ (len * c1 + c2)).  A sum, so
 // any lane may add any byte.  mix64 = splitmix64's finaliser.

@@ -137,6 +137,11 @@ SIGNATURES = {
     "vcfxg_merge_files": (_I, [_VP, _VP, _VP]),
     "vcfxg_merge_order": (_I, [_VP, _U64, _U64, _VP]),
     "vcfxg_merge_text": (_I, [_VP, _U64, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "vcfxg_regions_load": (_I, [_VP, _VP, _VP, ctypes.c_uint32, _VP, _VP, _VP, _U64, _VP]),
+    "vcfxg_regions_merged": (_I, [_VP, _VP, _VP, _VP, _U64, ctypes.POINTER(_U64)]),
+    "vcfxg_region_filter": (_I, [_VP, _I, ctypes.POINTER(Summary)]),
+    "vcfxg_region_status": (_I, [_VP, _U64, _U64, _VP]),
+    "vcfxg_region_counts": (_I, [_VP, _VP]),
     "vcfxg_multiallelic_split": (_I, [_VP, _U64, _U64, _VP, ctypes.POINTER(Summary)]),
     "vcfxg_ms_line_ranges": (_I, [_VP, _U64, _U64, _VP]),
     "vcfxg_fasta_scan": (_I, [_VP, _U64, _U64, _I, ctypes.c_uint32, ctypes.POINTER(Summary)]),
@@ -470,6 +475,49 @@ class Engine:
         self._chk(self.L.vcfxg_dedup_status(self.h, 0, s.n_lines, st.ctypes.data), "dedup_status")
         cnt = np.zeros(6, np.uint64)
         self._chk(self.L.vcfxg_dedup_counts(self.h, cnt.ctypes.data), "dedup_counts")
+        return s, st[:s.n_lines], tuple(int(x) for x in cnt)
+
+    def regions_load(self, names, chrom_id, start1, end, hash_bits=0):
+        """VCFX_region_subsampler's table (vcfxg_regions_load): names = the distinct chromosome names
+        (bytes), and per interval its name's index, 1-based start and end.  hash_bits 1..63 keeps
+        only that many low bits of the names' hash (forces collisions in the dictionary).  The table
+        stays resident until the next call."""
+        import numpy as np
+        blob = b"".join(names)
+        off = np.zeros(len(names) + 1, np.uint64)
+        if names:
+            off[1:] = np.cumsum([len(x) for x in names], dtype=np.uint64)
+        cid = np.ascontiguousarray(chrom_id, np.uint32)
+        s1 = np.ascontiguousarray(start1, np.int32)
+        e = np.ascontiguousarray(end, np.int32)
+        assert len(cid) == len(s1) == len(e)
+        p = ctypes.c_uint32(int(hash_bits))  # vcfxg_rs_params
+        self._chk(self.L.vcfxg_regions_load(self.h, blob, off.ctypes.data, len(names), cid.ctypes.data, s1.ctypes.data,
+                                            e.ctypes.data, len(cid), ctypes.byref(p)), "regions_load")
+
+    def regions_merged(self):
+        """the resident table's merged intervals in (name index, start) order (vcfxg_regions_merged):
+        a list of (name index, start, end)"""
+        import numpy as np
+        n = _U64(0)
+        self._chk(self.L.vcfxg_regions_merged(self.h, None, None, None, 0, ctypes.byref(n)), "regions_merged")
+        k = int(n.value)
+        cid, s1, e = np.zeros(max(k, 1), np.uint32), np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.int32)
+        self._chk(self.L.vcfxg_regions_merged(self.h, cid.ctypes.data, s1.ctypes.data, e.ctypes.data, k, ctypes.byref(n)),
+                  "regions_merged")
+        return list(zip(cid[:k].tolist(), s1[:k].tolist(), e[:k].tolist()))
+
+    def region_filter(self, mode):
+        """VCFX_region_subsampler's decision over the indexed lines against the resident table
+        (index(0) and regions_load first; vcfxg_region_filter).  Returns (summary, statuses uint8
+        per line: VCFXG_RS_*, counts per status + the wave-path lines)."""
+        import numpy as np
+        s = Summary()
+        self._chk(self.L.vcfxg_region_filter(self.h, int(mode), ctypes.byref(s)), "region_filter")
+        st = np.zeros(max(int(s.n_lines), 1), np.uint8)
+        self._chk(self.L.vcfxg_region_status(self.h, 0, s.n_lines, st.ctypes.data), "region_status")
+        cnt = np.zeros(8, np.uint64)
+        self._chk(self.L.vcfxg_region_counts(self.h, cnt.ctypes.data), "region_counts")
         return s, st[:s.n_lines], tuple(int(x) for x in cnt)
 
     def sort(self, mode, natural=False):
