@@ -846,6 +846,59 @@ int vcfxg_region_filter(vcfxg_ctx *ctx, int mode, vcfxg_summary *out);
 int vcfxg_region_status(vcfxg_ctx *ctx, uint64_t first, uint64_t count, uint8_t *status);
 int vcfxg_region_counts(const vcfxg_ctx *ctx, uint64_t counts[8]);
 
+/* ---- VCFX_haplotype_extractor (the first segmentation, the first variable-width transpose) -------
+ * Over the indexed lines (vcfxg_index from the first data line: the caller has read the header and
+ * knows the n_samples names).  Lines end at '\n'; one trailing '\r' is stripped.  Per line status:
+ *   VCFXG_HX_EMPTY     an empty line (VCFXG_MODE_FILE: also a line of '\r' alone), skipped
+ *   VCFXG_HX_HEADER    a line that starts with '#', skipped (later "#CHROM" lines too)
+ *   VCFXG_HX_SHORT     fewer than 10 fields: "Warning: skipping invalid VCF line (<10 fields)"
+ *                      (VCFXG_MODE_STDIN: also a line of '\r' alone, VCFX_haplotype_extractor.cpp:739-744)
+ *   VCFXG_HX_BADPOS    a byte of POS is no digit: "Warning: invalid POS => skip variant"
+ *   VCFXG_HX_NOGT      FORMAT has no key that is exactly GT: dropped silently
+ *   VCFXG_HX_UNPHASED  a named sample has no field, an empty GT sub-field or one without '|':
+ *                      "Warning: Not all samples phased at CHROM:POS."
+ *   VCFXG_HX_MEMBER    a phased variant: a member of a block
+ * pos is the parsed POS (an empty POS is 0) from VCFXG_HX_NOGT up, else 0.  Members are numbered in line
+ * order; member m opens a block unless it has member m - 1's CHROM bytes, pos[m] - pos[m - 1] <=
+ * block_size (signed) and, with check, no sample flips (both GTs of at least 3 bytes, first and last
+ * bytes a, b then c, d with a != c, b != d, a == d, b == c).  flip = the first such sample of a pair
+ * that passed CHROM and distance under check, else n_samples.  Off the members member and block are
+ * ~0 and flip is ~0.
+ * vcfxg_haplotype_scan: statuses, POS, members, blocks, flips (rows = members, data_lines = blocks,
+ * general_records = the members that are not fixed-stride -- FORMAT exactly GT and every sample "a|b" --
+ * and so hold a row of the cell matrix).
+ * vcfxg_haplotype_blocks: the block table and the rows' layout (rows = blocks, text_bytes = the rows'
+ * bytes): row b is "CHROM\tSTART\tEND" of its first / last member, then per sample a tab and its GTs
+ * joined by '|', then '\n', at row_off[b] (64-bit), row_len[b] bytes.
+ * vcfxg_haplotype_text: the rows written into the context's text (vcfxg_fetch_text_range).
+ * A cell of the device's matrix is VCFXG_HX_CELL_BYTES: a 32-bit offset and a 32-bit length, so no GT of
+ * a line shorter than 2 GiB is too long for it.  Outside the domain: POS above 2147483647, a NUL byte. */
+#define VCFXG_HX_EMPTY 0
+#define VCFXG_HX_HEADER 1
+#define VCFXG_HX_SHORT 2
+#define VCFXG_HX_BADPOS 3
+#define VCFXG_HX_NOGT 4
+#define VCFXG_HX_UNPHASED 5
+#define VCFXG_HX_MEMBER 6
+#define VCFXG_HX_TILE_MEMBERS 32
+#define VCFXG_HX_TILE_SAMPLES 64
+#define VCFXG_HX_CELL_BYTES 8
+typedef struct {
+    int mode;            /* VCFXG_MODE_FILE / VCFXG_MODE_STDIN */
+    uint32_t n_samples;  /* the names of the first "#CHROM" line (>= 1) */
+    int64_t block_size;  /* -b */
+    int check;           /* -c */
+} vcfxg_hx_params;
+int vcfxg_haplotype_scan(vcfxg_ctx *ctx, const vcfxg_hx_params *params, vcfxg_summary *out);
+/* lines [first, first + count) of the last scan (any pointer may be NULL) */
+int vcfxg_haplotype_lines(vcfxg_ctx *ctx, uint64_t first, uint64_t count, uint8_t *status, int64_t *pos, uint64_t *member,
+                          uint64_t *block, uint32_t *flip);
+int vcfxg_haplotype_blocks(vcfxg_ctx *ctx, vcfxg_summary *out);
+/* blocks [first, first + count) of the last vcfxg_haplotype_blocks (any pointer may be NULL) */
+int vcfxg_haplotype_table(vcfxg_ctx *ctx, uint64_t first, uint64_t count, uint64_t *first_member, uint64_t *last_member,
+                          int64_t *start, int64_t *end, uint64_t *row_off, uint64_t *row_len);
+int vcfxg_haplotype_text(vcfxg_ctx *ctx, vcfxg_summary *out);
+
 /* ---- VCFX_haplotype_phaser (LD reuse in block phasing) ------------------
  * Over the lines from data_start (the byte after the '#CHROM' line): per line status 1 variant,
  * 4 '#' line, 3 "<10 fields", 7 invalid POS, 8 no GT in FORMAT, 0 empty (mode VCFXG_MODE_FILE:

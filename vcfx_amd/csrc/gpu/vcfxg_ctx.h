@@ -219,6 +219,17 @@ struct vcfxg_ctx {
     uint64_t rs_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     bool rs_loaded = false;  // a table is resident
     bool rs_done = false;    // c->status holds the last vcfxg_region_filter's statuses (of this index)
+    // VCFX_haplotype_extractor: per line POS, member flag and its scan, CHROM's length, the fixed-stride region's
+    // offset, the matrix-row flag and its scan, member / block / flip;
+    // the cell matrix (lines x samples); member -> line, block-start flags and their scan, flips; per block
+    // first and last member, START, END, head bytes, row length and its scan; per (tile, sample) the tile
+    // sums and carries, per tile its start flag; per (block, sample) the run's offset in the row; the last
+    // scan's parameters and counts
+    DevBuf hx_pos, hx_flag, hx_mnum, hx_clen, hx_fixed, hx_general, hx_gnum, hx_lmember, hx_lblock, hx_lflip, hx_cells, hx_mline, hx_start, hx_bnum, hx_flip,
+        hx_first, hx_last, hx_bstart, hx_bend, hx_head, hx_rowlen, hx_rowoff, hx_agg, hx_carry, hx_tstart, hx_base;
+    uint64_t hx_nm = 0, hx_nb = 0, hx_text = 0;
+    uint32_t hx_ns = 0;
+    bool hx_scanned = false, hx_laid = false;
     // VCFX_multiallelic_splitter: the table; per line of the block its tab offsets, cost and the
     // scans of nAlts and cost; each line's text offset; {lines taken, rows}; the last call's block;
     // lines and text bytes per call (read when the context opens; tests make blocks of one line)

@@ -633,6 +633,49 @@ hipError_t launch_rs_class(const char *buf, int64_t data_start, const uint64_t *
                            const RsTableArgs *table, uint8_t *status, uint32_t *queue, unsigned long long *counters,
                            hipStream_t s);
 
+// VCFX_haplotype_extractor (vcfxg_hx.hip) over the n indexed lines.  launch_hx_scan: per line its status
+// (kHx*), POS, member flag, CHROM's length and, for a member, its n_samples cells (GT offset in the line |
+// length << 32: kHxCellBytes each) in row `line` of the line-major matrix; a fixed-stride member (FORMAT
+// "GT", every sample "a|b") stores none: fixed[line] = its sample region's offset (0 otherwise), cell s
+// being (fixed + 4 s, 3); general[line] = a member with a matrix row.  launch_hx_members (mnum: the
+// exclusive scan of the flags): member -> line, and per line its member number (~0 off the members, where
+// lblock and lflip are ~0 too).  launch_hx_break: start[m] = member m opens a block, flip[m] = the first
+// sample that flips against member m - 1 (n_samples: none; examined only under check and when CHROM and
+// the signed POS difference let m extend).  launch_hx_blocks (bnum: the exclusive scan of start, nm + 1
+// entries): each block's first and last member, block and flip per line.  launch_hx_layout: tiles of
+// kHxTileMembers x kHxTileSamples; agg and carry hx_tiles(nm) x n_samples, tstart hx_tiles(nm); base nb x
+// n_samples = the exclusive sum along the samples of the block's per-sample widths; head = the bytes of
+// "CHROM\tSTART\tEND", row_len = the row with its '\n' (row_len[nb] is the caller's to zero for the scan).
+// launch_hx_heads / launch_hx_emit: the rows at row_off (the exclusive scan of row_len) into text.
+enum : uint8_t { kHxEmpty = 0, kHxHeader = 1, kHxShort = 2, kHxBadPos = 3, kHxNoGt = 4, kHxUnphased = 5, kHxMember = 6 };
+constexpr uint32_t kHxTileMembers = 32;
+constexpr uint32_t kHxTileSamples = 64;
+constexpr uint32_t kHxCellBytes = 8;
+uint64_t hx_tiles(uint64_t nm);
+hipError_t launch_hx_scan(const char *buf, int64_t data_start, const uint64_t *line_end, uint64_t n, int stdin_mode,
+                          uint32_t n_samples, uint8_t *status, int64_t *pos, uint32_t *flag, uint32_t *chrom_len,
+                          uint32_t *fixed, uint32_t *general, uint64_t *cells, hipStream_t s);
+hipError_t launch_hx_members(uint64_t n, const uint32_t *flag, const uint64_t *mnum, uint64_t *mline, uint64_t *lmember,
+                             uint64_t *lblock, uint32_t *lflip, hipStream_t s);
+hipError_t launch_hx_break(const char *buf, int64_t data_start, const uint64_t *line_end, uint64_t nm, const uint64_t *mline,
+                           const int64_t *pos, const uint32_t *chrom_len, const uint32_t *fixed, const uint64_t *cells,
+                           uint32_t n_samples, int64_t block_size, int check, uint32_t *start, uint32_t *flip, hipStream_t s);
+hipError_t launch_hx_blocks(uint64_t nm, const uint64_t *mline, const uint32_t *start, const uint64_t *bnum,
+                            const uint32_t *flip, uint64_t *first, uint64_t *last, uint64_t *lblock, uint32_t *lflip,
+                            hipStream_t s);
+hipError_t launch_hx_layout(uint64_t nm, uint64_t nb, uint32_t n_samples, const uint64_t *mline, const uint32_t *start,
+                            const uint64_t *bnum, const uint32_t *fixed, const uint64_t *cells, const uint64_t *first,
+                            const uint64_t *last, const int64_t *pos, const uint32_t *chrom_len, uint64_t *agg, uint32_t *tstart, uint64_t *carry,
+                            uint64_t *base, uint32_t *head, uint64_t *row_len, int64_t *bstart, int64_t *bend,
+                            hipStream_t s);
+hipError_t launch_hx_heads(const char *buf, int64_t data_start, const uint64_t *line_end, uint64_t nb, const uint64_t *first,
+                           const uint64_t *mline, const uint32_t *chrom_len, const int64_t *bstart, const int64_t *bend,
+                           const uint64_t *row_off, const uint64_t *row_len, char *text, hipStream_t s);
+hipError_t launch_hx_emit(const char *buf, int64_t data_start, const uint64_t *line_end, uint64_t nm, uint32_t n_samples,
+                          const uint64_t *mline, const uint32_t *start, const uint64_t *bnum, const uint32_t *fixed,
+                          const uint64_t *cells, const uint64_t *carry, const uint64_t *base, const uint32_t *head,
+                          const uint64_t *row_off, char *text, hipStream_t s);
+
 // The ordered-text stage of the sorter, the merger and the diff tool (vcfxg_gather.hip).
 // launch_line_len: len[j] = the bytes of output line j = indexed line order[j] with its '\n', src[j] =
 // its first input byte (len[nw] = 0).  launch_text_gather: output lines [first, first + k) (off: the

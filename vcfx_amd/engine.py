@@ -42,6 +42,12 @@ class MsParams(ctypes.Structure):
     _fields_ = [("table", ctypes.c_void_p), ("n_entries", ctypes.c_uint64), ("mode", ctypes.c_int)]
 
 
+class HxParams(ctypes.Structure):
+    """vcfxg_hx_params"""
+    _fields_ = [("mode", ctypes.c_int), ("n_samples", ctypes.c_uint32), ("block_size", ctypes.c_int64),
+                ("check", ctypes.c_int)]
+
+
 class FaParams(ctypes.Structure):
     _fields_ = [("mode", ctypes.c_int), ("n_samples", ctypes.c_uint32), ("first_col", ctypes.c_uint64),
                 ("total_cols", ctypes.c_uint64), ("row_off", ctypes.c_void_p), ("skip", ctypes.c_void_p)]
@@ -144,6 +150,11 @@ SIGNATURES = {
     "vcfxg_region_counts": (_I, [_VP, _VP]),
     "vcfxg_multiallelic_split": (_I, [_VP, _U64, _U64, _VP, ctypes.POINTER(Summary)]),
     "vcfxg_ms_line_ranges": (_I, [_VP, _U64, _U64, _VP]),
+    "vcfxg_haplotype_scan": (_I, [_VP, _VP, ctypes.POINTER(Summary)]),
+    "vcfxg_haplotype_lines": (_I, [_VP, _U64, _U64, _VP, _VP, _VP, _VP, _VP]),
+    "vcfxg_haplotype_blocks": (_I, [_VP, ctypes.POINTER(Summary)]),
+    "vcfxg_haplotype_table": (_I, [_VP, _U64, _U64, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "vcfxg_haplotype_text": (_I, [_VP, ctypes.POINTER(Summary)]),
     "vcfxg_fasta_scan": (_I, [_VP, _U64, _U64, _I, ctypes.c_uint32, ctypes.POINTER(Summary)]),
     "vcfxg_fasta_status": (_I, [_VP, _U64, _U64, _VP, _VP]),
     "vcfxg_fasta_begin": (_I, [_VP, _U64]),
@@ -649,6 +660,39 @@ class Engine:
         if n:
             self._chk(self.L.vcfxg_ms_line_ranges(self.h, l0, n, off.ctypes.data), "ms_line_ranges")
         return s, st[:n], alt[:n], off, self.text(s.text_bytes)
+
+    def haplotype_scan(self, n_samples, block_size=100000, check=False, mode=MODE_FILE):
+        """VCFX_haplotype_extractor's decisions over the indexed lines (index(first data line) first;
+        vcfxg_haplotype_scan).  Returns (summary: rows = members, data_lines = blocks; per line status
+        uint8 VCFXG_HX_*, pos int64, member, block (uint64, ~0 off the members), flip (uint32: the first
+        flipping sample, n_samples for none, ~0 off the members))."""
+        import numpy as np
+        p = HxParams(int(mode), int(n_samples), int(block_size), int(bool(check)))
+        s = Summary()
+        self._chk(self.L.vcfxg_haplotype_scan(self.h, ctypes.byref(p), ctypes.byref(s)), "haplotype_scan")
+        n = int(s.n_lines)
+        st, pos = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.int64)
+        mem, blk, flip = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint32)
+        self._chk(self.L.vcfxg_haplotype_lines(self.h, 0, n, st.ctypes.data, pos.ctypes.data, mem.ctypes.data,
+                                               blk.ctypes.data, flip.ctypes.data), "haplotype_lines")
+        return s, st[:n], pos[:n], mem[:n], blk[:n], flip[:n]
+
+    def haplotype_blocks(self):
+        """the block table of the last haplotype_scan (vcfxg_haplotype_blocks): (summary: rows = blocks,
+        text_bytes; per block first member, last member, start, end, row offset, row length)"""
+        import numpy as np
+        s = Summary()
+        self._chk(self.L.vcfxg_haplotype_blocks(self.h, ctypes.byref(s)), "haplotype_blocks")
+        nb = int(s.rows)
+        a = [np.zeros(max(nb, 1), t) for t in (np.uint64, np.uint64, np.int64, np.int64, np.uint64, np.uint64)]
+        self._chk(self.L.vcfxg_haplotype_table(self.h, 0, nb, *[x.ctypes.data for x in a]), "haplotype_table")
+        return (s,) + tuple(x[:nb] for x in a)
+
+    def haplotype_text(self):
+        """the rows of the last haplotype_blocks written on the device (vcfxg_haplotype_text): their bytes"""
+        s = Summary()
+        self._chk(self.L.vcfxg_haplotype_text(self.h, ctypes.byref(s)), "haplotype_text")
+        return self.text_range(0, int(s.text_bytes)) if s.text_bytes else b""
 
     def fasta_scan(self, l0, l1, n_samples, mode=MODE_FILE):
         """VCFX_fasta_converter's statuses over indexed lines [l0, l1) (vcfxg_fasta_scan; stdin mode
