@@ -8,14 +8,14 @@ ARCH ?= gfx950
 B := build
 GPU_SRC := vcfx_amd/csrc/gpu
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Iinclude -I$(GPU_SRC) $(EXTRA_HIPFLAGS)
-GPU_OBJS := $(B)/obj/vcfxg_kernels.o $(B)/obj/vcfxg_rf.o $(B)/obj/vcfxg_ld.o $(B)/obj/vcfxg_ld_fast.o $(B)/obj/vcfxg_ld_mask.o $(B)/obj/vcfxg_af_walk.o $(B)/obj/vcfxg_fq_walk.o $(B)/obj/vcfxg_hwe.o $(B)/obj/vcfxg_dose.o $(B)/obj/vcfxg_md.o $(B)/obj/vcfxg_ac.o $(B)/obj/vcfxg_ph.o $(B)/obj/vcfxg_ib.o $(B)/obj/vcfxg_sx.o $(B)/obj/vcfxg_cc.o $(B)/obj/vcfxg_dd.o $(B)/obj/vcfxg_ms.o $(B)/obj/vcfxg_fa.o $(B)/obj/vcfxg_srt.o $(B)/obj/vcfxg_df.o $(B)/obj/vcfxg_mg.o $(B)/obj/vcfxg_rs.o $(B)/obj/vcfxg_hx.o $(B)/obj/vcfxg_gather.o $(B)/obj/vcfxg_inflate.o $(B)/obj/vcfxg_decimal.o \
-            $(patsubst %,$(B)/obj/vcfxg_%.o,api api_bgzf api_walk api_af api_fq api_hwe api_ib api_cc api_dd api_ms api_fa api_srt api_df api_mg api_rs api_hx api_keyed api_dose api_lines api_ld comm)
+GPU_OBJS := $(B)/obj/vcfxg_kernels.o $(B)/obj/vcfxg_rf.o $(B)/obj/vcfxg_ld.o $(B)/obj/vcfxg_ld_fast.o $(B)/obj/vcfxg_ld_mask.o $(B)/obj/vcfxg_af_walk.o $(B)/obj/vcfxg_fq_walk.o $(B)/obj/vcfxg_hwe.o $(B)/obj/vcfxg_dose.o $(B)/obj/vcfxg_md.o $(B)/obj/vcfxg_ac.o $(B)/obj/vcfxg_ph.o $(B)/obj/vcfxg_ib.o $(B)/obj/vcfxg_sx.o $(B)/obj/vcfxg_cc.o $(B)/obj/vcfxg_dd.o $(B)/obj/vcfxg_ms.o $(B)/obj/vcfxg_fa.o $(B)/obj/vcfxg_srt.o $(B)/obj/vcfxg_df.o $(B)/obj/vcfxg_mg.o $(B)/obj/vcfxg_rs.o $(B)/obj/vcfxg_hx.o $(B)/obj/vcfxg_fx.o $(B)/obj/vcfxg_gather.o $(B)/obj/vcfxg_inflate.o $(B)/obj/vcfxg_decimal.o \
+            $(patsubst %,$(B)/obj/vcfxg_%.o,api api_bgzf api_walk api_af api_fq api_hwe api_ib api_cc api_dd api_ms api_fa api_srt api_df api_mg api_rs api_hx api_fx api_keyed api_dose api_lines api_ld comm)
 
 TOOLS := VCFX_allele_freq_calc VCFX_genotype_query VCFX_record_filter VCFX_variant_counter VCFX_ld_calculator \
          VCFX_nonref_filter VCFX_hwe_tester VCFX_dosage_calculator VCFX_missing_detector VCFX_allele_counter \
          VCFX_haplotype_phaser VCFX_inbreeding_calculator VCFX_sample_extractor VCFX_cross_sample_concordance \
          VCFX_duplicate_remover VCFX_multiallelic_splitter VCFX_fasta_converter VCFX_sorter VCFX_diff_tool VCFX_merger \
-         VCFX_region_subsampler VCFX_haplotype_extractor
+         VCFX_region_subsampler VCFX_haplotype_extractor VCFX_field_extractor
 HOST_SRC := vcfx_amd/csrc/host
 TOOL_SRC := vcfx_amd/csrc/tools
 CXXFLAGS := -O2 -std=c++17 -fPIC -Wall -Wno-unused-result -Iinclude -I$(HOST_SRC) -I$(TOOL_SRC)
@@ -182,6 +182,11 @@ $(SAN)/host_rs_asan: tests/host_rs_test.cpp $(TOOL_SRC)/rs_host.h
 # VCFX_haplotype_extractor's host-only code (std::stoi for -b, the header rule, the names, the GT spans, the
 # warning and debug texts: hx_host.h) under ASan + UBSan; built by its own test (tests/test_host_hx.py)
 $(SAN)/host_hx_asan: tests/host_hx_test.cpp $(TOOL_SRC)/hx_host.h
+	@mkdir -p $(dir $@)
+	$(CXX) $(SANFLAGS) -I$(TOOL_SRC) -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
+# VCFX_field_extractor's host-only code (the --fields split, the field forms of both modes, the S<n> check, the
+# names, the table builder: fx_host.h) under ASan + UBSan; built by its own test (tests/test_host_fx.py)
+$(SAN)/host_fx_asan: tests/host_fx_test.cpp $(TOOL_SRC)/fx_host.h include/vcfx_gpu.h
 	@mkdir -p $(dir $@)
 	$(CXX) $(SANFLAGS) -I$(TOOL_SRC) -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
 # threshold_bounds (vcfxg_decimal.cpp: plain C++, no HIP) under ASan + UBSan: doubles' bit patterns in,

@@ -899,6 +899,69 @@ int vcfxg_haplotype_table(vcfxg_ctx *ctx, uint64_t first, uint64_t count, uint64
                           int64_t *start, int64_t *end, uint64_t *row_off, uint64_t *row_len);
 int vcfxg_haplotype_text(vcfxg_ctx *ctx, vcfxg_summary *out);
 
+/* ---- VCFX_field_extractor (the first projection: records to a TSV of named cells) ---------------
+ * Over the indexed lines (vcfxg_index from offset 0).  Lines end at '\n'; VCFXG_MODE_FILE strips one
+ * trailing '\r' first, VCFXG_MODE_STDIN strips nothing.  Per line status:
+ *   VCFXG_FX_EMPTY   an empty line, skipped
+ *   VCFXG_FX_HEADER  a line that starts with '#', skipped
+ *   VCFXG_FX_ROW     every other line: one row of n_cols cells
+ * An output column (vcfxg_fx_col) is
+ *   VCFXG_FX_STD     field `col` (0..7) of the line
+ *   VCFXG_FX_INFO    the value of the INFO key (key_off, key_len: bytes of the pool).  VCFXG_MODE_FILE
+ *                    (findInfoValue, VCFX_field_extractor.cpp:191-225): pairs split at ';', the key ends at
+ *                    the pair's first '=', the FIRST matching pair wins, a pair without '=' is the flag "1",
+ *                    an INFO of no byte or of exactly "." holds nothing.  VCFXG_MODE_STDIN (parseInfo
+ *                    :538-558): an INFO whose first byte is '.' holds nothing, empty pairs are skipped, the
+ *                    LAST matching pair wins.
+ *   VCFXG_FX_SAMPLE  the colon token of field `col` (>= 9; 0: no such column) whose index is that of the
+ *                    first FORMAT token equal to the sub-field (sub_off, sub_len).  named: col came from a
+ *                    name of the first "#CHROM" line and holds only for the lines that start at or after
+ *                    names_from.  VCFXG_MODE_STDIN asks INFO for the key (the whole field) first (:602).
+ *   VCFXG_FX_NONE    nothing: always "."
+ * A cell is VCFXG_FX_CELL_BYTES: a 32-bit offset from the line's start and a 32-bit length, or offset 0
+ * and the length word VCFXG_FX_DOT (the text ".": a missing column, key, sample or sub-field, and in
+ * VCFXG_MODE_FILE an empty value) or VCFXG_FX_ONE (the text "1": a flag).  A row is its cells' bytes
+ * joined by tabs and a '\n'.  The matrix is line-major, one row of n_cols cells per indexed line (the
+ * cells of a line that is no row are not written): one pass fills it, before the rows are numbered.
+ * vcfxg_fields_load: the table; it outlives loads and indexes of the input.
+ * vcfxg_fields_scan: statuses, the matrix, row numbers (the scan of the statuses) and 64-bit row offsets
+ *   (the scan of the rows' bytes): rows, text_bytes; general_records = 1 when the table did not fit
+ *   VCFXG_FX_TABLE_LDS bytes of LDS and was read from global memory, else 0.
+ * vcfxg_fields_text: the rows written into the context's text (vcfxg_fetch_text_range), tiles of
+ *   VCFXG_FX_TILE_ROWS lines through an LDS stage of VCFXG_FX_STAGE bytes.
+ * Outside the domain: a NUL byte, a line of 2 GiB or more, a sample index above 2147483638. */
+#define VCFXG_FX_EMPTY 0
+#define VCFXG_FX_HEADER 1
+#define VCFXG_FX_ROW 2
+#define VCFXG_FX_STD 0
+#define VCFXG_FX_INFO 1
+#define VCFXG_FX_SAMPLE 2
+#define VCFXG_FX_NONE 3
+#define VCFXG_FX_DOT 0xFFFFFFFFu
+#define VCFXG_FX_ONE 0xFFFFFFFEu
+#define VCFXG_FX_NOKEY 0xFFFFFFFFu
+#define VCFXG_FX_CELL_BYTES 8
+#define VCFXG_FX_TABLE_LDS 16384
+#define VCFXG_FX_TILE_ROWS 64
+#define VCFXG_FX_STAGE 8192
+typedef struct {
+    uint32_t kind;             /* VCFXG_FX_STD / _INFO / _SAMPLE / _NONE */
+    uint32_t col;              /* STD: 0..7; SAMPLE: the line's column (>= 9), 0: none */
+    uint32_t named;            /* SAMPLE: col is a name's column */
+    uint32_t key_off, key_len; /* INFO, and SAMPLE in VCFXG_MODE_STDIN; key_len VCFXG_FX_NOKEY: no key */
+    uint32_t sub_off, sub_len; /* SAMPLE: the sub-field */
+    uint32_t reserved;
+} vcfxg_fx_col;
+int vcfxg_fields_load(vcfxg_ctx *ctx, const vcfxg_fx_col *cols, uint32_t n_cols, const char *pool, uint32_t pool_bytes,
+                      int mode);
+int vcfxg_fields_scan(vcfxg_ctx *ctx, uint64_t names_from, vcfxg_summary *out);
+/* lines [first, first + count) of the last scan (any pointer may be NULL): status, the rows before the
+ * line, the text bytes before the line */
+int vcfxg_fields_lines(vcfxg_ctx *ctx, uint64_t first, uint64_t count, uint8_t *status, uint64_t *row, uint64_t *row_off);
+/* the matrix rows of lines [first, first + count): count * n_cols cells of two uint32_t each */
+int vcfxg_fields_cells(vcfxg_ctx *ctx, uint64_t first, uint64_t count, uint32_t *cells);
+int vcfxg_fields_text(vcfxg_ctx *ctx, vcfxg_summary *out);
+
 /* ---- VCFX_haplotype_phaser (LD reuse in block phasing) ------------------
  * Over the lines from data_start (the byte after the '#CHROM' line): per line status 1 variant,
  * 4 '#' line, 3 "<10 fields", 7 invalid POS, 8 no GT in FORMAT, 0 empty (mode VCFXG_MODE_FILE:

@@ -31,6 +31,7 @@
  *   vcfx_tool_merger  run/main, VCFX_merger.cpp:94-148, 355-361 (K files, no stdin)
  *   vcfx_tool_region_subsampler  run/main, VCFX_region_subsampler.cpp:254-324, 574-580
  *   vcfx_tool_haplotype_extractor  main, VCFX_haplotype_extractor.cpp:826-911
+ *   vcfx_tool_field_extractor  main, VCFX_field_extractor.cpp:709-773
  *   vcfx_tool_main              the `vcfx <tool> ...` dispatch (src/vcfx_wrapper/vcfx.cpp:177-187)
  * Without a usable gfx950 device a tool that reaches the record loop writes
  * "no usable MI355X" to err_fd and returns 1 (no CPU fallback).
@@ -66,6 +67,7 @@ vcfx_entry_fn vcfx_tool_diff_tool;
 vcfx_entry_fn vcfx_tool_merger;
 vcfx_entry_fn vcfx_tool_region_subsampler;
 vcfx_entry_fn vcfx_tool_haplotype_extractor;
+vcfx_entry_fn vcfx_tool_field_extractor;
 /* tool = "VCFX_<name>" (a leading path is ignored); -100 for an unknown tool */
 int vcfx_tool_main(const char *tool, int argc, char **argv, int in_fd, int out_fd, int err_fd);
 /* The same invocation over ngpu device contexts in this process (one host thread per rank;

@@ -16,7 +16,7 @@ TOOLS_LIB = os.path.join(BUILD, "libvcfx_tools.so")
 SYNTH_LIB = os.path.join(BUILD, "libvcfx_synth.so")
 TOOLS = ("VCFX_allele_freq_calc", "VCFX_record_filter", "VCFX_genotype_query", "VCFX_ld_calculator",
          "VCFX_variant_counter", "VCFX_fasta_converter", "VCFX_sorter", "VCFX_diff_tool", "VCFX_merger",
-         "VCFX_region_subsampler", "VCFX_haplotype_extractor")
+         "VCFX_region_subsampler", "VCFX_haplotype_extractor", "VCFX_field_extractor")
 
 
 def tool_binary(tool):

@@ -210,7 +210,7 @@ void vcfxg_close(vcfxg_ctx *c) {
     for (DevBuf *b : {&c->input, &c->idx_counts, &c->idx_offs, &c->idx_pos, &c->line_end, &c->d_nlines, &c->scan_tmp, &c->alt,
                       &c->tot, &c->rowpre, &c->status, &c->rowlen, &c->rowoff, &c->text, &c->counters, &c->query, &c->crit, &c->pool, &c->ld_G, &c->ld_lines,
                       &c->ld_vidx, &c->ld_valid, &c->ld_Gc, &c->ld_wcnt, &c->ld_wval, &c->ld_vbase, &c->ld_small, &c->ld_pend, &c->ld_vars, &c->ld_plen, &c->ld_poff, &c->ld_prefix,
-                      &c->ld_cid, &c->ld_blocks, &c->ld_cnt, &c->ld_off, &c->ld_pairs, &c->ld_fast, &c->ld_gflag, &c->ld_Gp, &c->ld_Gv, &c->ld_Gq, &c->dose_meta, &c->af_meta, &c->ld_temp, &c->ld_quarters, &c->ld_stage_ctr, &c->ld_rowoff, &c->async_small, &c->wk_le, &c->wk_alt, &c->wk_tot, &c->wk_rowpre, &c->wk_status, &c->wk_meta, &c->wk_count, &c->wk_offs, &c->wk_gt, &c->wk_small, &c->wk_tabs, &c->rf_tabs, &c->hwe_aux, &c->wk_aux, &c->hwe_rc, &c->wk_text, &c->wk_toff, &c->wk_start, &c->wk_cx, &c->wk_bs, &c->scratch_small, &c->byte_cnt, &c->ld_moff, &c->ld_midx, &c->ld_mvar, &c->ld_gt16, &c->ld_sprec, &c->ld_midx16, &c->bgz_in, &c->bgz_mem, &c->bgz_off, &c->bgz_stat, &c->bgz_small, &c->bgz_perm, &c->ib_codes, &c->ib_meta, &c->ib_tab, &c->ib_packed, &c->ib_cnt, &c->ib_offs, &c->ib_sum, &c->ib_obs, &c->ib_used, &c->ib_carried, &c->ib_small, &c->sx_mask, &c->cc_mult, &c->cc_isdata, &c->cc_ord, &c->cc_chrom, &c->cc_small, &c->dd_tabs, &c->dd_pos, &c->dd_hash, &c->dd_queue, &c->dd_isdata, &c->dd_ord, &c->dd_hp, &c->dd_head, &c->dd_left, &c->srt_pos, &c->srt_aux, &c->srt_w0, &c->srt_queue, &c->srt_written, &c->srt_ord, &c->df_tabs, &c->df_klen, &c->df_koff, &c->df_ntok, &c->df_posv, &c->df_natv, &c->df_nsuf, &c->df_hash, &c->df_isdata, &c->df_ord, &c->df_queue, &c->df_ktext, &c->df_line, &c->df_hp, &c->df_head, &c->df_rep, &c->df_first2, &c->df_left, &c->df_state, &c->df_uflag, &c->df_uord, &c->df_sum, &c->mg_file, &c->mg_pos, &c->mg_w0, &c->mg_ks, &c->mg_kl, &c->mg_pn, &c->mg_num, &c->mg_queue, &c->mg_written, &c->mg_ord, &c->mg_fmeta, &c->mg_state, &c->fa_flag, &c->fa_col, &c->fa_meta, &c->fa_M, &c->fa_rowoff, &c->fa_skip, &c->rs_tab, &c->rs_names, &c->rs_noff, &c->rs_dict, &c->rs_in, &c->rs_sid, &c->rs_start, &c->rs_key, &c->rs_tile, &c->rs_reach, &c->rs_first, &c->rs_last, &c->rs_open, &c->rs_ord, &c->rs_mid, &c->rs_mstart, &c->rs_mend, &c->rs_queue, &c->hx_pos, &c->hx_flag, &c->hx_mnum, &c->hx_clen, &c->hx_fixed, &c->hx_general, &c->hx_gnum, &c->hx_lmember, &c->hx_lblock, &c->hx_lflip, &c->hx_cells, &c->hx_mline, &c->hx_start, &c->hx_bnum, &c->hx_flip, &c->hx_first, &c->hx_last, &c->hx_bstart, &c->hx_bend, &c->hx_head, &c->hx_rowlen, &c->hx_rowoff, &c->hx_agg, &c->hx_carry, &c->hx_tstart, &c->hx_base})
+                      &c->ld_cid, &c->ld_blocks, &c->ld_cnt, &c->ld_off, &c->ld_pairs, &c->ld_fast, &c->ld_gflag, &c->ld_Gp, &c->ld_Gv, &c->ld_Gq, &c->dose_meta, &c->af_meta, &c->ld_temp, &c->ld_quarters, &c->ld_stage_ctr, &c->ld_rowoff, &c->async_small, &c->wk_le, &c->wk_alt, &c->wk_tot, &c->wk_rowpre, &c->wk_status, &c->wk_meta, &c->wk_count, &c->wk_offs, &c->wk_gt, &c->wk_small, &c->wk_tabs, &c->rf_tabs, &c->hwe_aux, &c->wk_aux, &c->hwe_rc, &c->wk_text, &c->wk_toff, &c->wk_start, &c->wk_cx, &c->wk_bs, &c->scratch_small, &c->byte_cnt, &c->ld_moff, &c->ld_midx, &c->ld_mvar, &c->ld_gt16, &c->ld_sprec, &c->ld_midx16, &c->bgz_in, &c->bgz_mem, &c->bgz_off, &c->bgz_stat, &c->bgz_small, &c->bgz_perm, &c->ib_codes, &c->ib_meta, &c->ib_tab, &c->ib_packed, &c->ib_cnt, &c->ib_offs, &c->ib_sum, &c->ib_obs, &c->ib_used, &c->ib_carried, &c->ib_small, &c->sx_mask, &c->cc_mult, &c->cc_isdata, &c->cc_ord, &c->cc_chrom, &c->cc_small, &c->dd_tabs, &c->dd_pos, &c->dd_hash, &c->dd_queue, &c->dd_isdata, &c->dd_ord, &c->dd_hp, &c->dd_head, &c->dd_left, &c->srt_pos, &c->srt_aux, &c->srt_w0, &c->srt_queue, &c->srt_written, &c->srt_ord, &c->df_tabs, &c->df_klen, &c->df_koff, &c->df_ntok, &c->df_posv, &c->df_natv, &c->df_nsuf, &c->df_hash, &c->df_isdata, &c->df_ord, &c->df_queue, &c->df_ktext, &c->df_line, &c->df_hp, &c->df_head, &c->df_rep, &c->df_first2, &c->df_left, &c->df_state, &c->df_uflag, &c->df_uord, &c->df_sum, &c->mg_file, &c->mg_pos, &c->mg_w0, &c->mg_ks, &c->mg_kl, &c->mg_pn, &c->mg_num, &c->mg_queue, &c->mg_written, &c->mg_ord, &c->mg_fmeta, &c->mg_state, &c->fa_flag, &c->fa_col, &c->fa_meta, &c->fa_M, &c->fa_rowoff, &c->fa_skip, &c->rs_tab, &c->rs_names, &c->rs_noff, &c->rs_dict, &c->rs_in, &c->rs_sid, &c->rs_start, &c->rs_key, &c->rs_tile, &c->rs_reach, &c->rs_first, &c->rs_last, &c->rs_open, &c->rs_ord, &c->rs_mid, &c->rs_mstart, &c->rs_mend, &c->rs_queue, &c->hx_pos, &c->hx_flag, &c->hx_mnum, &c->hx_clen, &c->hx_fixed, &c->hx_general, &c->hx_gnum, &c->hx_lmember, &c->hx_lblock, &c->hx_lflip, &c->hx_cells, &c->hx_mline, &c->hx_start, &c->hx_bnum, &c->hx_flip, &c->hx_first, &c->hx_last, &c->hx_bstart, &c->hx_bend, &c->hx_head, &c->hx_rowlen, &c->hx_rowoff, &c->hx_agg, &c->hx_carry, &c->hx_tstart, &c->hx_base, &c->fx_tab, &c->fx_out, &c->fx_status, &c->fx_isrow, &c->fx_rownum, &c->fx_rowlen, &c->fx_rowoff, &c->fx_cells, &c->fx_span, &c->fx_sub})
         if (b->p) (void)hipFree(b->p);
     for (SortScratch *s : {&c->dd_sort, &c->srt_sort, &c->df_sort, &c->mg_sort, &c->rs_sort})
         for (DevBuf *b : {&s->k0, &s->k1, &s->v0, &s->v1, &s->tmp})
@@ -453,6 +453,7 @@ int vcfxg_index(vcfxg_ctx *c, size_t data_start, uint64_t *n_lines) {
     c->mg_done = false;
     c->rs_done = false;
     c->hx_scanned = c->hx_laid = false;
+    c->fx_scanned = false;
     c->ms_done = false;
     c->fa_scanned = c->fa_begun = false;
     if (!c->loaded) return VCFXG_E_STATE;

@@ -230,6 +230,18 @@ struct vcfxg_ctx {
     uint64_t hx_nm = 0, hx_nb = 0, hx_text = 0;
     uint32_t hx_ns = 0;
     bool hx_scanned = false, hx_laid = false;
+    // VCFX_field_extractor: the table of the last vcfxg_fields_load (it outlives loads and indexes of the
+    // input) and its counts; per line the status, the row flag and its scan, the row bytes and their scan, the cell
+    // matrix (lines x columns), the requested sample columns' spans and the sub-fields' FORMAT indices (the
+    // cell pass's scratch); the last scan's rows and text bytes
+    DevBuf fx_tab, fx_out, fx_status, fx_isrow, fx_rownum, fx_rowlen, fx_rowoff, fx_cells, fx_span, fx_sub;
+    std::vector<uint32_t> fx_tab_host;
+    vcfxg::FxOut fx_out_host = {};  // host sources / destinations of the scan's asynchronous copies
+    uint64_t fx_tail[2] = {0, 0};
+    uint32_t fx_ncols = 0, fx_nsc = 0, fx_nsub = 0;
+    uint64_t fx_rows = 0, fx_text = 0;
+    bool fx_loaded = false;   // a table is resident
+    bool fx_scanned = false;  // the statuses and the matrix are the last vcfxg_fields_scan's (of this index and table)
     // VCFX_multiallelic_splitter: the table; per line of the block its tab offsets, cost and the
     // scans of nAlts and cost; each line's text offset; {lines taken, rows}; the last call's block;
     // lines and text bytes per call (read when the context opens; tests make blocks of one line)

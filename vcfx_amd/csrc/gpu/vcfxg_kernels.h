@@ -676,6 +676,43 @@ hipError_t launch_hx_emit(const char *buf, int64_t data_start, const uint64_t *l
                           const uint64_t *cells, const uint64_t *carry, const uint64_t *base, const uint32_t *head,
                           const uint64_t *row_off, char *text, hipStream_t s);
 
+// VCFX_field_extractor (vcfxg_fx.hip) over the n indexed lines.  The table is one array of 32-bit words
+// in device memory (the kernels take its pointer, never a descriptor by value): kFxHWords header words
+// (kFxH*: counts, then the word offsets of the parts), per output column {kind kFx*, standard column},
+// per INFO key {pool offset, length, output column}, per distinct sub-field {pool offset, length}, per
+// sample cell {output column, line column (0: none), index among the requested columns, sub-field |
+// named << 31}, the requested sample columns as nwords + 2 mask words (bit f = column f; two zero words
+// behind) and nwords + 1 rank words (set bits before the word), the pool's bytes.  launch_fx_cells: per
+// line its status (kFxEmpty / kFxHeader / kFxRow), row flag, row bytes and, for a row, its ncols cells
+// {offset, length | kFxDot | kFxOne} in row `line` of the line-major matrix; spans (n x nsc x 2 words)
+// and subidx (n x nsub words) are its scratch (all through an FxOut in device memory).  A named cell holds for the lines that start at or after
+// names_from.  launch_fx_write: the rows at rowoff (the exclusive scan of the row bytes, n + 1 entries)
+// into text (16 B aligned).
+enum : uint8_t { kFxEmpty = 0, kFxHeader = 1, kFxRow = 2 };
+enum : uint32_t { kFxStd = 0, kFxInfo = 1, kFxSample = 2, kFxNone = 3 };
+constexpr uint32_t kFxDot = 0xFFFFFFFFu, kFxOne = 0xFFFFFFFEu;
+constexpr uint32_t kFxTableLds = 16384;  // table bytes kept in LDS; larger: global loads
+constexpr uint32_t kFxTileRows = 64;     // lines per block of k_fx_write
+constexpr uint32_t kFxStage = 8192;      // its LDS stage
+enum : uint32_t {
+    kFxHNcols = 0, kFxHNkeys, kFxHNsub, kFxHNsamp, kFxHNsc, kFxHLastk, kFxHNwords, kFxHStdin,
+    kFxHCols, kFxHKeys, kFxHSubs, kFxHSamp, kFxHMask, kFxHRank, kFxHPool, kFxHTotal, kFxHWords
+};
+inline bool fx_table_in_lds(uint32_t table_words) { return 4ull * table_words <= kFxTableLds; }
+struct FxOut {  // launch_fx_cells' line index and outputs, in device memory (the kernel loads a field where it uses it)
+    uint8_t *status;
+    uint32_t *isrow;
+    uint64_t *rowlen;
+    uint32_t *cells, *spans, *subidx;
+    uint64_t names_from;
+    const uint64_t *line_end;  // the n indexed lines: line i is [line_end[i - 1] + 1, line_end[i]), the first from data_start
+    int64_t data_start;
+};
+hipError_t launch_fx_cells(const char *buf, uint64_t n, const uint32_t *table, uint32_t table_words, const FxOut *out,
+                           hipStream_t s);
+hipError_t launch_fx_write(const char *buf, int64_t data_start, const uint64_t *line_end, uint64_t n, uint32_t ncols,
+                           const uint8_t *status, const uint64_t *rowoff, const uint32_t *cells, char *out, hipStream_t s);
+
 // The ordered-text stage of the sorter, the merger and the diff tool (vcfxg_gather.hip).
 // launch_line_len: len[j] = the bytes of output line j = indexed line order[j] with its '\n', src[j] =
 // its first input byte (len[nw] = 0).  launch_text_gather: output lines [first, first + k) (off: the

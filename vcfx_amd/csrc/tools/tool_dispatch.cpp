@@ -35,5 +35,6 @@ extern "C" int vcfx_tool_main(const char *tool, int argc, char **argv, int in_fd
     if (!strcmp(t, "VCFX_merger")) return vcfx_tool_merger(argc, argv, in_fd, out_fd, err_fd);
     if (!strcmp(t, "VCFX_region_subsampler")) return vcfx_tool_region_subsampler(argc, argv, in_fd, out_fd, err_fd);
     if (!strcmp(t, "VCFX_haplotype_extractor")) return vcfx_tool_haplotype_extractor(argc, argv, in_fd, out_fd, err_fd);
+    if (!strcmp(t, "VCFX_field_extractor")) return vcfx_tool_field_extractor(argc, argv, in_fd, out_fd, err_fd);
     return -100;
 }

@@ -48,6 +48,13 @@ class HxParams(ctypes.Structure):
                 ("check", ctypes.c_int)]
 
 
+class FxCol(ctypes.Structure):
+    """vcfxg_fx_col"""
+    _fields_ = [("kind", ctypes.c_uint32), ("col", ctypes.c_uint32), ("named", ctypes.c_uint32),
+                ("key_off", ctypes.c_uint32), ("key_len", ctypes.c_uint32), ("sub_off", ctypes.c_uint32),
+                ("sub_len", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 class FaParams(ctypes.Structure):
     _fields_ = [("mode", ctypes.c_int), ("n_samples", ctypes.c_uint32), ("first_col", ctypes.c_uint64),
                 ("total_cols", ctypes.c_uint64), ("row_off", ctypes.c_void_p), ("skip", ctypes.c_void_p)]
@@ -155,6 +162,11 @@ SIGNATURES = {
     "vcfxg_haplotype_blocks": (_I, [_VP, ctypes.POINTER(Summary)]),
     "vcfxg_haplotype_table": (_I, [_VP, _U64, _U64, _VP, _VP, _VP, _VP, _VP, _VP]),
     "vcfxg_haplotype_text": (_I, [_VP, ctypes.POINTER(Summary)]),
+    "vcfxg_fields_load": (_I, [_VP, _VP, ctypes.c_uint32, _VP, ctypes.c_uint32, _I]),
+    "vcfxg_fields_scan": (_I, [_VP, _U64, ctypes.POINTER(Summary)]),
+    "vcfxg_fields_lines": (_I, [_VP, _U64, _U64, _VP, _VP, _VP]),
+    "vcfxg_fields_cells": (_I, [_VP, _U64, _U64, _VP]),
+    "vcfxg_fields_text": (_I, [_VP, ctypes.POINTER(Summary)]),
     "vcfxg_fasta_scan": (_I, [_VP, _U64, _U64, _I, ctypes.c_uint32, ctypes.POINTER(Summary)]),
     "vcfxg_fasta_status": (_I, [_VP, _U64, _U64, _VP, _VP]),
     "vcfxg_fasta_begin": (_I, [_VP, _U64]),
@@ -692,6 +704,40 @@ class Engine:
         """the rows of the last haplotype_blocks written on the device (vcfxg_haplotype_text): their bytes"""
         s = Summary()
         self._chk(self.L.vcfxg_haplotype_text(self.h, ctypes.byref(s)), "haplotype_text")
+        return self.text_range(0, int(s.text_bytes)) if s.text_bytes else b""
+
+    def fields_load(self, cols, pool, mode=MODE_FILE):
+        """VCFX_field_extractor's table (vcfxg_fields_load): cols = (kind, col, named, key_off, key_len,
+        sub_off, sub_len) per output column (kinds and VCFXG_FX_NOKEY as in vcfx_gpu.h), pool = the keys'
+        and sub-fields' bytes.  The table stays on the context."""
+        arr = (FxCol * max(len(cols), 1))()
+        for i, c in enumerate(cols):
+            arr[i] = FxCol(*[int(x) for x in c], 0)
+        self._fx_ncols = len(cols)
+        self._chk(self.L.vcfxg_fields_load(self.h, ctypes.cast(arr, ctypes.c_void_p), len(cols), bytes(pool), len(pool),
+                                           int(mode)), "fields_load")
+
+    def fields_scan(self, names_from=0xFFFFFFFFFFFFFFFF):
+        """the cell pass over the indexed lines against the resident table (index(0) first;
+        vcfxg_fields_scan): (summary: rows, text_bytes, general_records = the table was read from global
+        memory; per line status uint8 VCFXG_FX_*, the rows before it, the text bytes before it (uint64);
+        the matrix of the ROW lines, rows x columns x (offset, length) uint32).  A named cell holds for the
+        lines that start at or after byte names_from."""
+        import numpy as np
+        s = Summary()
+        self._chk(self.L.vcfxg_fields_scan(self.h, int(names_from), ctypes.byref(s)), "fields_scan")
+        n, nc = int(s.n_lines), self._fx_ncols
+        st, row, off = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint64)
+        cells = np.zeros((max(n, 1), nc, 2), np.uint32)
+        self._chk(self.L.vcfxg_fields_lines(self.h, 0, n, st.ctypes.data, row.ctypes.data, off.ctypes.data), "fields_lines")
+        self._chk(self.L.vcfxg_fields_cells(self.h, 0, n, cells.ctypes.data), "fields_cells")
+        st = st[:n]
+        return s, st, row[:n], off[:n], cells[:n][st == 2]
+
+    def fields_text(self):
+        """the rows of the last fields_scan written on the device (vcfxg_fields_text): their bytes"""
+        s = Summary()
+        self._chk(self.L.vcfxg_fields_text(self.h, ctypes.byref(s)), "fields_text")
         return self.text_range(0, int(s.text_bytes)) if s.text_bytes else b""
 
     def fasta_scan(self, l0, l1, n_samples, mode=MODE_FILE):
