@@ -117,7 +117,8 @@ sanitize: $(SAN)/host_san_asan $(SAN)/host_san_tsan $(SAN)/core_api_asan $(SAN)/
     $(if $(wildcard tests/host_ms_test.cpp),$(SAN)/host_ms_asan) \
     $(if $(wildcard tests/host_fa_test.cpp),$(SAN)/host_fa_asan) \
     $(if $(wildcard tests/decimal_bounds_test.cpp),$(SAN)/decimal_bounds_asan) \
-    $(if $(wildcard tests/walk_layout_test.cpp),$(SAN)/walk_layout_asan)
+    $(if $(wildcard tests/walk_layout_test.cpp),$(SAN)/walk_layout_asan) \
+    $(if $(wildcard tests/env_knobs_test.cpp),$(SAN)/env_knobs_asan)
 $(SAN)/host_san_asan: $(SAN_HOST_SRC) $(wildcard $(HOST_SRC)/*.h) $(B)/libvcfx_gpu.so
 	@mkdir -p $(dir $@)
 	$(CXX) $(SANFLAGS) -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $(SAN_HOST_SRC) \
@@ -198,6 +199,11 @@ $(SAN)/decimal_bounds_asan: tests/decimal_bounds_test.cpp $(GPU_SRC)/vcfxg_decim
 # the record walk's chunk layout (vcfxg_walk_layout.h: plain C++, shared by the kernel and the plan)
 # under ASan + UBSan: cases in, every walker's bytes out (tests/test_walk_layout_cpu.py checks the tiling)
 $(SAN)/walk_layout_asan: tests/walk_layout_test.cpp $(GPU_SRC)/vcfxg_walk_layout.h
+	@mkdir -p $(dir $@)
+	$(CXX) $(SANFLAGS) -I$(GPU_SRC) -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
+# the context's environment-knob reader (vcfxg_env.h: plain C++) under ASan + UBSan: cases in, the values
+# read out (tests/test_env_knobs_cpu.py sets the environment)
+$(SAN)/env_knobs_asan: tests/env_knobs_test.cpp $(GPU_SRC)/vcfxg_env.h
 	@mkdir -p $(dir $@)
 	$(CXX) $(SANFLAGS) -I$(GPU_SRC) -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $<
 .PHONY: sanitize

@@ -29,7 +29,9 @@ enum vcfxg_status {
     VCFXG_E_HIP = -2,     /* HIP runtime error (vcfxg_last_error has the text) */
     VCFXG_E_ARG = -3,     /* bad argument */
     VCFXG_E_NOMEM = -4,   /* device or host allocation failed */
-    VCFXG_E_STATE = -5,   /* call out of order (e.g. no input loaded / not indexed) */
+    VCFXG_E_STATE = -5,   /* call out of order (e.g. no input loaded / not indexed; a result fetch whose
+                             call has not run on the current index; a status fetch after another call
+                             has written the context's per-line statuses) */
     VCFXG_E_CAP = -6,     /* caller buffer too small */
     VCFXG_E_DATA = -7     /* the input data is invalid (a BGZF member that does not inflate as zlib would) */
 };
@@ -61,6 +63,9 @@ const char *vcfxg_version(void);
 int vcfxg_device_count(int *n);
 int vcfxg_open(int device, vcfxg_ctx **out);
 void vcfxg_close(vcfxg_ctx *ctx);
+/* the device bytes that the buffers of every open context of this process hold (their capacities):
+ * exact, and back at its earlier value once a context is closed */
+uint64_t vcfxg_device_bytes_live(void);
 const char *vcfxg_last_error(const vcfxg_ctx *ctx);
 /* the hipStream_t every call of this context is ordered on */
 void *vcfxg_stream(vcfxg_ctx *ctx);

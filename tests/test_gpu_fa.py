@@ -53,7 +53,7 @@ def test_golden_binary():
                            timeout=120)
         return (r.returncode, r.stdout, r.stderr) == (case["rc"], case["stdout"], case["stderr"])
 
-    with ThreadPoolExecutor(16) as ex:
+    with ThreadPoolExecutor(12) as ex:  # (with this process, under the 16 that may have the device open)
         ok = list(ex.map(one, CASES))
     assert all(ok), [c["name"] for c, v in zip(CASES, ok) if not v]
 

@@ -24,12 +24,19 @@ int ensure(vcfxg_ctx *c, DevBuf &b, size_t bytes) {
     size_t nc = bytes < 4096 ? 4096 : bytes + bytes / 8;
     if (b.p) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipFree(b.p));
-        b.p = nullptr;
-        b.cap = 0;
+        HIPCHK(c, b.release());
     }
-    HIPCHK(c, hipMalloc(&b.p, nc));
-    b.cap = nc;
+    HIPCHK(c, b.alloc(nc));
+    return VCFXG_OK;
+}
+
+int regrow(vcfxg_ctx *c, DevBuf &b, size_t bytes, size_t keep) {
+    DevBuf nb;
+    HIPCHK(c, nb.alloc(bytes));
+    if (keep && b.p) HIPCHK(c, hipMemcpyAsync(nb.p, b.p, keep, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, b.release());
+    b = std::move(nb);
     return VCFXG_OK;
 }
 
@@ -156,7 +163,7 @@ bool load_hints(vcfxg_ctx *c, const char *h, size_t n) {
     // long records want longer chunks (GT:AD:DP, 30 KB records: 128 KiB 5.03 ms, 512 KiB 4.76,
     // 1 MiB 5.10; r03 sweep; r05, XCD-contiguous walker blocks: 256 KiB 3.73 ms, 384 KiB 3.65,
     // 512 KiB 3.69, 768 KiB 3.89).  VCFXG_WALK_CHUNK overrides.
-    if (!getenv("VCFXG_WALK_CHUNK"))
+    if (!c->walk_chunk_forced)
         c->walk_chunk = c->hint_line > 16 * 1024
                             ? std::min<int64_t>(((12 * c->hint_line + 65535) / 65536) * 65536, 4 << 20)
                             : 128 * 1024;
@@ -203,27 +210,12 @@ int vcfxg_open(int device, vcfxg_ctx **out) {
     return VCFXG_OK;
 }
 
+// (the device made current and the stream drained here, the buffers freed by their owners when the
+// context is deleted at the end)
 void vcfxg_close(vcfxg_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (DevBuf *b : {&c->input, &c->idx_counts, &c->idx_offs, &c->idx_pos, &c->line_end, &c->d_nlines, &c->scan_tmp, &c->alt,
-                      &c->tot, &c->rowpre, &c->status, &c->rowlen, &c->rowoff, &c->text, &c->counters, &c->query, &c->crit, &c->pool, &c->ld_G, &c->ld_lines,
-                      &c->ld_vidx, &c->ld_valid, &c->ld_Gc, &c->ld_wcnt, &c->ld_wval, &c->ld_vbase, &c->ld_small, &c->ld_pend, &c->ld_vars, &c->ld_plen, &c->ld_poff, &c->ld_prefix,
-                      &c->ld_cid, &c->ld_blocks, &c->ld_cnt, &c->ld_off, &c->ld_pairs, &c->ld_fast, &c->ld_gflag, &c->ld_Gp, &c->ld_Gv, &c->ld_Gq, &c->dose_meta, &c->af_meta, &c->ld_temp, &c->ld_quarters, &c->ld_stage_ctr, &c->ld_rowoff, &c->async_small, &c->wk_le, &c->wk_alt, &c->wk_tot, &c->wk_rowpre, &c->wk_status, &c->wk_meta, &c->wk_count, &c->wk_offs, &c->wk_gt, &c->wk_small, &c->wk_tabs, &c->rf_tabs, &c->hwe_aux, &c->wk_aux, &c->hwe_rc, &c->wk_text, &c->wk_toff, &c->wk_start, &c->wk_cx, &c->wk_bs, &c->scratch_small, &c->byte_cnt, &c->ld_moff, &c->ld_midx, &c->ld_mvar, &c->ld_gt16, &c->ld_sprec, &c->ld_midx16, &c->bgz_in, &c->bgz_mem, &c->bgz_off, &c->bgz_stat, &c->bgz_small, &c->bgz_perm, &c->ib_codes, &c->ib_meta, &c->ib_tab, &c->ib_packed, &c->ib_cnt, &c->ib_offs, &c->ib_sum, &c->ib_obs, &c->ib_used, &c->ib_carried, &c->ib_small, &c->sx_mask, &c->cc_mult, &c->cc_isdata, &c->cc_ord, &c->cc_chrom, &c->cc_small, &c->dd_tabs, &c->dd_pos, &c->dd_hash, &c->dd_queue, &c->dd_isdata, &c->dd_ord, &c->dd_hp, &c->dd_head, &c->dd_left, &c->srt_pos, &c->srt_aux, &c->srt_w0, &c->srt_queue, &c->srt_written, &c->srt_ord, &c->df_tabs, &c->df_klen, &c->df_koff, &c->df_ntok, &c->df_posv, &c->df_natv, &c->df_nsuf, &c->df_hash, &c->df_isdata, &c->df_ord, &c->df_queue, &c->df_ktext, &c->df_line, &c->df_hp, &c->df_head, &c->df_rep, &c->df_first2, &c->df_left, &c->df_state, &c->df_uflag, &c->df_uord, &c->df_sum, &c->mg_file, &c->mg_pos, &c->mg_w0, &c->mg_ks, &c->mg_kl, &c->mg_pn, &c->mg_num, &c->mg_queue, &c->mg_written, &c->mg_ord, &c->mg_fmeta, &c->mg_state, &c->fa_flag, &c->fa_col, &c->fa_meta, &c->fa_M, &c->fa_rowoff, &c->fa_skip, &c->rs_tab, &c->rs_names, &c->rs_noff, &c->rs_dict, &c->rs_in, &c->rs_sid, &c->rs_start, &c->rs_key, &c->rs_tile, &c->rs_reach, &c->rs_first, &c->rs_last, &c->rs_open, &c->rs_ord, &c->rs_mid, &c->rs_mstart, &c->rs_mend, &c->rs_queue, &c->hx_pos, &c->hx_flag, &c->hx_mnum, &c->hx_clen, &c->hx_fixed, &c->hx_general, &c->hx_gnum, &c->hx_lmember, &c->hx_lblock, &c->hx_lflip, &c->hx_cells, &c->hx_mline, &c->hx_start, &c->hx_bnum, &c->hx_flip, &c->hx_first, &c->hx_last, &c->hx_bstart, &c->hx_bend, &c->hx_head, &c->hx_rowlen, &c->hx_rowoff, &c->hx_agg, &c->hx_carry, &c->hx_tstart, &c->hx_base, &c->fx_tab, &c->fx_out, &c->fx_status, &c->fx_isrow, &c->fx_rownum, &c->fx_rowlen, &c->fx_rowoff, &c->fx_cells, &c->fx_span, &c->fx_sub})
-        if (b->p) (void)hipFree(b->p);
-    for (SortScratch *s : {&c->dd_sort, &c->srt_sort, &c->df_sort, &c->mg_sort, &c->rs_sort})
-        for (DevBuf *b : {&s->k0, &s->k1, &s->v0, &s->v1, &s->tmp})
-            if (b->p) (void)hipFree(b->p);
-    for (TextOrder *t : {&c->srt_out, &c->df_out, &c->mg_out})
-        for (DevBuf *b : {&t->len, &t->off, &t->src})
-            if (b->p) (void)hipFree(b->p);
-    for (DevBuf &b : c->bgz_tok)
-        if (b.p) (void)hipFree(b.p);
-    if (c->af_small.p) (void)hipFree(c->af_small.p);
-    if (c->wk_stage.p) (void)hipFree(c->wk_stage.p);
-    if (c->wk_dirty.p) (void)hipFree(c->wk_dirty.p);
-    if (c->fq_small.p) (void)hipFree(c->fq_small.p);
     if (c->sum_host) (void)hipHostFree(c->sum_host);
     for (auto &pe : c->ingest_ev) (void)hipEventDestroy(pe.second);
     for (hipEvent_t e : c->ingest_ev_free) (void)hipEventDestroy(e);
@@ -245,6 +237,8 @@ void vcfxg_close(vcfxg_ctx *c) {
         if (e) (void)hipEventDestroy(e);
     delete c;
 }
+
+uint64_t vcfxg_device_bytes_live(void) { return DevBuf::live.load(); }
 
 const char *vcfxg_last_error(const vcfxg_ctx *c) { return c ? c->err.c_str() : "no context"; }
 void *vcfxg_stream(vcfxg_ctx *c) { return c ? (void *)c->stream : nullptr; }
@@ -294,7 +288,7 @@ static void reset_hints(vcfxg_ctx *c) {
     c->walk_overflowed = false;
     c->dose_head_failed = false;
     c->ph_head_failed = false;
-    if (!getenv("VCFXG_WALK_CHUNK")) c->walk_chunk = 128 * 1024;
+    if (!c->walk_chunk_forced) c->walk_chunk = 128 * 1024;
 }
 
 int vcfxg_load_host(vcfxg_ctx *c, const char *host, size_t n) {
@@ -305,8 +299,8 @@ int vcfxg_load_host(vcfxg_ctx *c, const char *host, size_t n) {
 }
 
 int vcfxg_ingest_begin(vcfxg_ctx *c, size_t size_hint) {
-    if (c) c->dense_pending = false;  // a new index / regions replace the pending ones
     if (!c) return VCFXG_E_ARG;
+    new_index(c);
     HIPCHK(c, hipSetDevice(c->device));
     // (a staged BGZF stream abandoned before vcfxg_ingest_bgzf may still have copies and inflate
     // batches in flight on their own streams: they finish before the input is written again)
@@ -340,14 +334,8 @@ int vcfxg_ingest(vcfxg_ctx *c, const char *host, size_t n, int is_final_chunk) {
     HIPCHK(c, hipSetDevice(c->device));
     if (c->n + n + kPad > c->input.cap) {
         // grow: a larger buffer, the bytes so far copied on the device
-        size_t nc = std::max(c->input.cap * 2, c->n + n + kPad);
-        void *np = nullptr;
-        HIPCHK(c, hipMalloc(&np, nc));
-        if (c->n) HIPCHK(c, hipMemcpyAsync(np, c->input.p, c->n, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipFree(c->input.p));
-        c->input.p = np;
-        c->input.cap = nc;
+        const int r = regrow(c, c->input, std::max(c->input.cap * 2, c->n + n + kPad), c->n);
+        if (r) return r;
     }
     // pageable host memory: the runtime's staged DMA runs at the PCIe rate (measured
     // 50-56 GB/s on MI355X, tools/microbench/h2d_ingest.cpp), asynchronous to the caller
@@ -445,17 +433,8 @@ int vcfxg_input_fetch(vcfxg_ctx *c, uint64_t offset, size_t n, void *host) {
 const void *vcfxg_input_device_ptr(vcfxg_ctx *c) { return c && c->loaded ? c->input.p : nullptr; }
 
 int vcfxg_index(vcfxg_ctx *c, size_t data_start, uint64_t *n_lines) {
-    if (c) c->dense_pending = false;  // a new index / regions replace the pending ones
     if (!c) return VCFXG_E_ARG;
-    c->dd_done = false;
-    c->srt_done = false;
-    c->df_done = false;
-    c->mg_done = false;
-    c->rs_done = false;
-    c->hx_scanned = c->hx_laid = false;
-    c->fx_scanned = false;
-    c->ms_done = false;
-    c->fa_scanned = c->fa_begun = false;
+    new_index(c);
     if (!c->loaded) return VCFXG_E_STATE;
     if (data_start > c->n) data_start = c->n;
     HIPCHK(c, hipSetDevice(c->device));

@@ -31,7 +31,7 @@ int vcfxg_allele_freq(vcfxg_ctx *c, int mode, vcfxg_summary *out) {
     DENSE(c);
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t L = c->n_lines;
-    int r = af_buffers(c, L);
+    int r = af_buffers(c, L, StatusOwner::other);
     if (r) return r;
     const char *buf = P<char>(c->input);
     const uint64_t *nl_dev = P<uint64_t>(c->d_nlines);
@@ -56,7 +56,7 @@ int vcfxg_allele_freq(vcfxg_ctx *c, int mode, vcfxg_summary *out) {
 // newlines than the scratch keeps, or more lines than the capacity) reruns the call on the
 // synchronous path.
 static int af_region_async(vcfxg_ctx *c, size_t data_start, int mode, vcfxg_summary *out) {
-    if (c) c->dense_pending = false;  // a new index / regions replace the pending ones
+    new_index(c);
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t lo = (int64_t)data_start, hi = (int64_t)c->n;
     const int64_t nc = vcfxg::idx_wchunks(lo, hi);
@@ -71,7 +71,7 @@ static int af_region_async(vcfxg_ctx *c, size_t data_start, int mode, vcfxg_summ
     if (!r) r = ensure(c, c->idx_offs, sizeof(uint64_t) * (size_t)(nc + 1));
     if (!r) r = ensure(c, c->idx_pos, sizeof(uint64_t) * (size_t)nc * pcap + 64);
     if (!r) r = ensure(c, c->line_end, 8 * (cap + 1));
-    if (!r) r = af_buffers(c, cap);
+    if (!r) r = af_buffers(c, cap, StatusOwner::other);
     if (!r) r = ensure(c, c->af_meta, vcfxg::af_meta_bytes() * (cap + 1));
     if (!r) r = ensure(c, c->async_small, 128);
     if (r) return r;
@@ -157,7 +157,7 @@ static int af_region_async(vcfxg_ctx *c, size_t data_start, int mode, vcfxg_summ
 // (ensure_dense).  A walker over its line capacity, or an overlong leftover list, reruns the
 // call on the two-sweep schedule (and later calls on this input use it directly).
 static int af_region_walk(vcfxg_ctx *c, size_t data_start, int mode, vcfxg_summary *out, bool gf = false) {
-    if (c) c->dense_pending = false;  // a new index / regions replace the pending ones
+    new_index(c);
     HIPCHK(c, hipSetDevice(c->device));
     const WalkPlan pl = walk_plan(c, data_start, 0, !gf);  // (the GT-only walk: the plan's layout)
     const int64_t lo = pl.lo, hi = pl.hi, nw = pl.nw;

@@ -41,14 +41,8 @@ static int bgz_tables(vcfxg_ctx *c, uint64_t want, uint64_t keep) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (const Tab &x : t) {
         if (x.b->cap >= x.w * want) continue;
-        const size_t nc = x.w * want + x.w * want / 8;
-        void *np = nullptr;
-        HIPCHK(c, hipMalloc(&np, nc));
-        if (keep && x.b->p) HIPCHK(c, hipMemcpyAsync(np, x.b->p, x.w * keep, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (x.b->p) HIPCHK(c, hipFree(x.b->p));
-        x.b->p = np;
-        x.b->cap = nc;
+        const int r = regrow(c, *x.b, x.w * want + x.w * want / 8, x.w * keep);
+        if (r) return r;
     }
     return VCFXG_OK;
 }
@@ -126,18 +120,12 @@ static uint64_t bgz_tokens(vcfxg_ctx *c, int k, uint64_t count, hipStream_t st) 
         if (b.cap >= want * per + 4) return want;
         if (b.p) {  // (the stream's earlier batches may still read it)
             if (hipStreamSynchronize(st) != hipSuccess) return 0;
-            (void)hipFree(b.p);
-            b.p = nullptr;
-            b.cap = 0;
+            (void)b.release();
         }
         // (rounded up to 8,192 members: a batch a few members past the last one's size reuses it)
         const uint64_t alloc = std::min<uint64_t>((want + 8191) / 8192 * 8192, std::max<uint64_t>(want, 69632));
-        if (hipMalloc(&b.p, alloc * per + 4) == hipSuccess) {
-            b.cap = alloc * per + 4;
-            return want;
-        }
+        if (b.alloc(alloc * per + 4) == hipSuccess) return want;
         (void)hipGetLastError();
-        b.p = nullptr;
         if (want <= 4096) return 0;
     }
 }
@@ -264,14 +252,8 @@ int vcfxg_ingest_bgzf(vcfxg_ctx *c, const void *comp, size_t comp_n, const vcfxg
     }
     if (c->n + tot + kPad > c->input.cap) {  // grow as vcfxg_ingest does (keeping launched output)
         const size_t keep = c->n + (size_t)(staged ? c->bgz_out : 0);
-        size_t ncap = std::max(c->input.cap * 2, c->n + tot + kPad);
-        void *np = nullptr;
-        HIPCHK(c, hipMalloc(&np, ncap));
-        if (keep) HIPCHK(c, hipMemcpyAsync(np, c->input.p, keep, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipFree(c->input.p));
-        c->input.p = np;
-        c->input.cap = ncap;
+        const int rg = regrow(c, c->input, std::max(c->input.cap * 2, c->n + tot + kPad), keep);
+        if (rg) return rg;
     }
     int r = VCFXG_OK;
     if (!staged) {

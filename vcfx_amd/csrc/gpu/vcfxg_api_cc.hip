@@ -13,7 +13,7 @@ extern "C" {
 // grown.  A walker over its line capacity reruns the call without the walk.
 static int cc_region_impl(vcfxg_ctx *c, size_t data_start, int mode, const vcfxg_cc_params *p, uint32_t ns,
                           vcfxg_summary *out, bool walk) {
-    c->dense_pending = false;  // a new index / regions replace the pending ones
+    new_index(c);
     HIPCHK(c, hipSetDevice(c->device));
     const WalkPlan pl = walk_plan(c, data_start);
     const int64_t lo = pl.lo;
@@ -40,7 +40,7 @@ static int cc_region_impl(vcfxg_ctx *c, size_t data_start, int mode, const vcfxg
             return VCFXG_OK;
         }
         cap = L;
-        r = af_buffers(c, cap);
+        r = af_buffers(c, cap, StatusOwner::other);
         if (r) return r;
         HIPCHK(c, hipMemsetAsync(c->wk_small.p, 0, 96, c->stream));
     }

@@ -23,14 +23,15 @@ int vcfxg_dedup(vcfxg_ctx *c, int mode, const vcfxg_dd_params *p, vcfxg_summary 
     const uint64_t L = c->n_lines;
     if (L >= (1ull << 31)) return VCFXG_E_ARG;  // (the scans and the sort count their items in an int)
     HIPCHK(c, hipSetDevice(c->device));
-    c->dd_done = false;
+    claim_status(c, StatusOwner::dedup);
+    c->dd_done = {};
     std::memset(c->dd_counts, 0, sizeof c->dd_counts);
     if (out) std::memset(out, 0, sizeof *out);
     if (!L) {
-        c->dd_done = true;
+        mark_done(c, c->dd_done);
         return VCFXG_OK;
     }
-    int r = ensure(c, c->status, L + 1);
+    int r = status_buffer(c, L, StatusOwner::dedup);
     if (!r) r = ensure(c, c->counters, 64);
     if (!r) r = ensure(c, c->dd_isdata, 4 * (L + 1));
     if (!r) r = ensure(c, c->dd_ord, 8 * (L + 1));
@@ -91,7 +92,7 @@ int vcfxg_dedup(vcfxg_ctx *c, int mode, const vcfxg_dd_params *p, vcfxg_summary 
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
     for (int i = 0; i < 6; i++) c->dd_counts[i] = cnt[i];
-    c->dd_done = true;
+    mark_done(c, c->dd_done);
     if (out) {
         out->n_lines = L;
         out->rows = cnt[VCFXG_DD_KEPT];
@@ -103,7 +104,7 @@ int vcfxg_dedup(vcfxg_ctx *c, int mode, const vcfxg_dd_params *p, vcfxg_summary 
 }
 
 int vcfxg_dedup_status(vcfxg_ctx *c, uint64_t first, uint64_t count, uint8_t *status) {
-    return c ? fetch_status(c, c->dd_done, first, count, status) : VCFXG_E_ARG;
+    return c ? fetch_status(c, StatusOwner::dedup, c->dd_done, first, count, status) : VCFXG_E_ARG;
 }
 
 int vcfxg_dedup_counts(const vcfxg_ctx *c, uint64_t counts[6]) {

@@ -28,7 +28,8 @@ int vcfxg_diff(vcfxg_ctx *c, const vcfxg_df_params *p, vcfxg_summary *out) {
     const uint64_t L = c->n_lines;
     if (L >= (1ull << 31)) return VCFXG_E_ARG;  // (the scans and the sort count their items in an int)
     HIPCHK(c, hipSetDevice(c->device));
-    c->df_done = false;
+    claim_status(c, StatusOwner::diff);
+    c->df_done = {};
     c->df_nu1 = 0;
     c->df_out.n = 0;
     c->df_out.off_host.clear();
@@ -37,10 +38,10 @@ int vcfxg_diff(vcfxg_ctx *c, const vcfxg_df_params *p, vcfxg_summary *out) {
     c->df_counts[6] = sorted ? VCFXG_DF_PATH_BOUNDS : VCFXG_DF_PATH_HASH;
     if (out) std::memset(out, 0, sizeof *out);
     if (!L) {
-        c->df_done = true;
+        mark_done(c, c->df_done);
         return VCFXG_OK;
     }
-    int r = ensure(c, c->status, L + 1);
+    int r = status_buffer(c, L, StatusOwner::diff);
     if (!r) r = ensure(c, c->counters, 128);
     if (!r) r = ensure(c, c->df_isdata, 4 * (L + 1));
     if (!r) r = ensure(c, c->df_ord, 8 * (L + 1));
@@ -169,7 +170,7 @@ int vcfxg_diff(vcfxg_ctx *c, const vcfxg_df_params *p, vcfxg_summary *out) {
     for (int i = 0; i < 8; i++)
         if (i != 6) c->df_counts[i] = sum[i];
     c->df_nu1 = sum[0];
-    c->df_done = true;
+    mark_done(c, c->df_done);
     if (out) {
         out->n_lines = L;
         out->rows = nu;
@@ -181,7 +182,7 @@ int vcfxg_diff(vcfxg_ctx *c, const vcfxg_df_params *p, vcfxg_summary *out) {
 }
 
 int vcfxg_diff_status(vcfxg_ctx *c, uint64_t first, uint64_t count, uint8_t *status) {
-    return c ? fetch_status(c, c->df_done, first, count, status) : VCFXG_E_ARG;
+    return c ? fetch_status(c, StatusOwner::diff, c->df_done, first, count, status) : VCFXG_E_ARG;
 }
 
 int vcfxg_diff_counts(const vcfxg_ctx *c, uint64_t counts[8]) {
@@ -196,7 +197,7 @@ int vcfxg_diff_text(vcfxg_ctx *c, int side, uint64_t first_out, uint64_t *taken,
     if (!c || (side != 0 && side != 1)) return VCFXG_E_ARG;
     if (taken) *taken = 0;
     if (bytes) *bytes = 0;
-    if (!c->indexed || !c->df_done) return VCFXG_E_STATE;
+    if (!c->indexed || !is_done(c, c->df_done)) return VCFXG_E_STATE;
     const uint64_t lo = side ? c->df_nu1 : 0, hi = side ? c->df_out.n : c->df_nu1;
     if (first_out > hi - lo) return VCFXG_E_ARG;
     return text_block(c, c->df_out, P<char>(c->df_ktext), lo + first_out, hi, c->df_block, "df_gather", taken, bytes);

@@ -11,7 +11,7 @@ extern "C" {
 // context is indexed afterwards.  *overflow: a walker ran out of line slots (short lines)
 static int dose_walk_index(vcfxg_ctx *c, size_t data_start, int mode, uint64_t *L_out, bool *overflow,
                            bool head) {
-    c->dense_pending = false;
+    new_index(c);
     HIPCHK(c, hipSetDevice(c->device));
     const WalkPlan pl = walk_plan(c, data_start);
     if (!pl.fits_gt16) {  // the caller's index path
@@ -90,7 +90,7 @@ static int dosage_region_once(vcfxg_ctx *c, size_t data_start, int mode, vcfxg_s
         if (r) return r;
     }
     HIPCHK(c, hipSetDevice(c->device));
-    r = af_buffers(c, L);
+    r = af_buffers(c, L, StatusOwner::other);
     if (!r) r = ensure(c, c->dose_meta, vcfxg::dose_meta_bytes() * (L + 1));
     if (r) return r;
     const char *buf = P<char>(c->input);
@@ -201,7 +201,7 @@ static int phaser_once(vcfxg_ctx *c, size_t data_start, int mode, double thr, ui
     static thread_local uint64_t h[2];
     for (int pass = 0;; pass++) {
         r = ensure(c, c->ph_G, L * kpad + 16);
-        if (!r) r = af_buffers(c, L);
+        if (!r) r = af_buffers(c, L, StatusOwner::other);
         if (!r) r = ensure(c, c->ph_isvar, 4 * (L + 1));
         if (!r) r = ensure(c, c->ph_info, vcfxg::ph_line_bytes() * (L + 1));
         if (!r) r = ensure(c, c->ph_vnum, 8 * (L + 1));

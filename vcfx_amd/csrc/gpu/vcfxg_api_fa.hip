@@ -14,7 +14,7 @@ static_assert(kFaEmpty == VCFXG_FA_EMPTY && kFaColumn == VCFXG_FA_COLUMN && kFaS
 // The block [l0, l0 + n): statuses, flags, FaMeta, column numbers; tail[0] = its columns,
 // tail[1] = its "#CHROM" lines (after a synchronisation).
 static int fa_scan_block(vcfxg_ctx *c, uint64_t l0, uint64_t n, int mode, uint32_t n_samples, uint64_t tail[2]) {
-    int r = af_buffers(c, c->n_lines);
+    int r = af_buffers(c, c->n_lines, StatusOwner::fasta);
     if (!r) r = ensure(c, c->fa_flag, 4 * (n + 1));
     if (!r) r = ensure(c, c->fa_col, 8 * (n + 1));
     if (!r) r = ensure(c, c->fa_meta, sizeof(FaMeta) * n);
@@ -36,9 +36,7 @@ static int fa_scan_block(vcfxg_ctx *c, uint64_t l0, uint64_t n, int mode, uint32
     c->fa_l0 = l0;
     c->fa_n = n;
     c->fa_cols = tail[0];
-    c->fa_scanned = true;
-    c->dd_done = false;  // (the statuses are this call's now)
-    c->ms_done = false;
+    mark_done(c, c->fa_scanned);
     return VCFXG_OK;
 }
 
@@ -55,7 +53,7 @@ int vcfxg_fasta_scan(vcfxg_ctx *c, uint64_t l0, uint64_t l1, int mode, uint32_t 
     if (l1 > c->n_lines) return VCFXG_E_ARG;
     l1 = std::min(l1, l0 + c->fa_block);
     HIPCHK(c, hipSetDevice(c->device));
-    c->fa_scanned = false;
+    c->fa_scanned = {};
     if (out) std::memset(out, 0, sizeof *out);
     if (l1 == l0) return VCFXG_OK;
     static thread_local uint64_t tail[2];
@@ -72,7 +70,7 @@ int vcfxg_fasta_scan(vcfxg_ctx *c, uint64_t l0, uint64_t l1, int mode, uint32_t 
 
 int vcfxg_fasta_status(vcfxg_ctx *c, uint64_t first, uint64_t count, uint8_t *status, uint64_t *col) {
     if (!c || (!status && !col && count)) return VCFXG_E_ARG;
-    if (!c->indexed || !c->fa_scanned) return VCFXG_E_STATE;
+    if (!c->indexed || !is_done(c, c->fa_scanned) || (status && c->status_owner != StatusOwner::fasta)) return VCFXG_E_STATE;
     if (first < c->fa_l0 || first + count > c->fa_l0 + c->fa_n) return VCFXG_E_ARG;
     if (!count) return VCFXG_OK;
     if (status)
@@ -92,18 +90,18 @@ int vcfxg_fasta_begin(vcfxg_ctx *c, uint64_t text_bytes) {
     if (r) return r;
     c->text_bytes = text_bytes;
     c->fa_text = text_bytes;
-    c->fa_begun = true;
+    mark_done(c, c->fa_begun);
     return VCFXG_OK;
 }
 
 int vcfxg_fasta(vcfxg_ctx *c, uint64_t l0, uint64_t l1, const vcfxg_fa_params *p, vcfxg_summary *out) {
     if (!p || !fa_args(c, l0, l1, p->mode) || (p->n_samples && !p->row_off)) return VCFXG_E_ARG;
-    if (!c->indexed || !c->fa_begun || c->text_bytes != c->fa_text) return VCFXG_E_STATE;
+    if (!c->indexed || !is_done(c, c->fa_begun) || c->text_bytes != c->fa_text) return VCFXG_E_STATE;
     DENSE(c);
     if (l1 > c->n_lines) return VCFXG_E_ARG;
     l1 = std::min(l1, l0 + c->fa_block);
     HIPCHK(c, hipSetDevice(c->device));
-    c->fa_scanned = false;
+    c->fa_scanned = {};
     if (out) std::memset(out, 0, sizeof *out);
     if (l1 == l0) return VCFXG_OK;
     const uint64_t n = l1 - l0, ns = p->n_samples;

@@ -43,7 +43,7 @@ int vcfxg_nonref_filter(vcfxg_ctx *c, int mode, vcfxg_summary *out) {
     DENSE(c);
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t L = c->n_lines;
-    int r = ensure(c, c->status, L + 1);
+    int r = status_buffer(c, L, StatusOwner::other);
     if (r) return r;
     HIPCHK(c, hipMemsetAsync(c->counters.p, 0, 64, c->stream));
     prof_begin(c, "nr_records");
@@ -73,7 +73,7 @@ int vcfxg_genotype_query(vcfxg_ctx *c, const char *query, size_t qlen, int stric
     DENSE(c);
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t L = c->n_lines;
-    int r = ensure(c, c->status, L + 1);
+    int r = status_buffer(c, L, StatusOwner::other);
     if (!r) r = ensure(c, c->query, qlen + 1);
     if (!r) r = ensure(c, c->af_meta, vcfxg::af_meta_bytes() * (L + 1));
     if (r) return r;
@@ -182,7 +182,7 @@ static int compile_criteria(vcfxg_ctx *c, const vcfxg_criterion *crit, int n) {
 }
 
 static int run_rf(vcfxg_ctx *c, const vcfxg_criterion *crit, int n, int and_logic, int keep_cr = 0) {
-    int r = ensure(c, c->status, c->n_lines + 1);
+    int r = status_buffer(c, c->n_lines, StatusOwner::other);
     if (!r) r = compile_criteria(c, crit, n);
     if (r) return r;
     prof_begin(c, "rf_records");
@@ -271,7 +271,7 @@ static int fq_region(vcfxg_ctx *c, size_t data_start, int what, const vcfxg_crit
                      const char *query, size_t qlen, int strict, int gq_strip_cr, vcfxg_summary *out) {
     if (!c || n < 0 || (n && !crit) || (!query && qlen)) return VCFXG_E_ARG;
     if (!c->loaded) return VCFXG_E_STATE;
-    c->dense_pending = false;  // its own index replaces pending regions
+    new_index(c);
     if (data_start > c->n) data_start = c->n;
     HIPCHK(c, hipSetDevice(c->device));
     const WalkPlan pl = walk_plan(c, data_start);
@@ -385,12 +385,12 @@ int vcfxg_nonref_filter_region(vcfxg_ctx *c, size_t data_start, int mode, vcfxg_
 // with the missing-allele reducer (one HBM pass; k_md_lines then takes the lines it left and
 // the flagged lines' INFO spans), else the line index and k_md_lines on every line
 static int md_region_walk(vcfxg_ctx *c, size_t data_start, int mode, vcfxg_summary *out) {
-    c->dense_pending = false;
+    new_index(c);
     HIPCHK(c, hipSetDevice(c->device));
     const WalkPlan pl = walk_plan(c, data_start);
     const int64_t lo = pl.lo;
     const uint64_t cap = pl.cap;
-    int r = af_buffers(c, cap);
+    int r = af_buffers(c, cap, StatusOwner::other);
     if (r) return r;
     const char *buf = P<char>(c->input);
     const vcfxg::RfArgs ra{nullptr, 0, 1, nullptr, 0};
@@ -436,7 +436,7 @@ int vcfxg_missing_region(vcfxg_ctx *c, size_t data_start, int mode, vcfxg_summar
     int r = vcfxg_index(c, data_start, &L);
     if (r) return r;
     HIPCHK(c, hipSetDevice(c->device));
-    r = af_buffers(c, L);
+    r = af_buffers(c, L, StatusOwner::other);
     if (r) return r;
     HIPCHK(c, hipMemsetAsync(c->counters.p, 0, 64, c->stream));
     prof_begin(c, "md_lines");
@@ -463,7 +463,7 @@ int vcfxg_variant_count(vcfxg_ctx *c, int strip_cr, vcfxg_summary *out) {
     if (!c->indexed) return VCFXG_E_STATE;
     DENSE(c);
     HIPCHK(c, hipSetDevice(c->device));
-    int r = ensure(c, c->status, c->n_lines + 1);
+    int r = status_buffer(c, c->n_lines, StatusOwner::other);
     if (r) return r;
     HIPCHK(c, hipMemsetAsync(c->counters.p, 0, 64, c->stream));
     prof_begin(c, "vc_records");

@@ -94,7 +94,8 @@ int vcfxg_fields_load(vcfxg_ctx *c, const vcfxg_fx_col *cols, uint32_t n, const 
     T[kFxHPool] = o;
     if (pool_bytes) std::memcpy(&T[o], pool, pool_bytes);
     T[kFxHTotal] = (uint32_t)total;
-    c->fx_loaded = c->fx_scanned = false;
+    c->fx_loaded = false;
+    c->fx_scanned = {};
     const int r = ensure(c, c->fx_tab, 4 * (size_t)total);
     if (r) return r;
     HIPCHK(c, hipMemcpyAsync(c->fx_tab.p, T.data(), 4 * (size_t)total, hipMemcpyHostToDevice, c->stream));
@@ -112,7 +113,7 @@ int vcfxg_fields_scan(vcfxg_ctx *c, uint64_t names_from, vcfxg_summary *out) {
     if (c->n_lines >= (1ull << 31)) return VCFXG_E_ARG;  // (the kernels hold line numbers in 32 bits)
     DENSE(c);
     HIPCHK(c, hipSetDevice(c->device));
-    c->fx_scanned = false;
+    c->fx_scanned = {};
     c->fx_rows = c->fx_text = 0;
     if (out) std::memset(out, 0, sizeof *out);
     const uint64_t n = c->n_lines, nc = c->fx_ncols;
@@ -153,7 +154,7 @@ int vcfxg_fields_scan(vcfxg_ctx *c, uint64_t names_from, vcfxg_summary *out) {
         c->fx_text = tail[1];
         prof_collect(c);
     }
-    c->fx_scanned = true;
+    mark_done(c, c->fx_scanned);
     if (out) {
         out->n_lines = n;
         out->rows = out->data_lines = c->fx_rows;
@@ -165,7 +166,7 @@ int vcfxg_fields_scan(vcfxg_ctx *c, uint64_t names_from, vcfxg_summary *out) {
 
 int vcfxg_fields_lines(vcfxg_ctx *c, uint64_t first, uint64_t count, uint8_t *status, uint64_t *row, uint64_t *row_off) {
     if (!c) return VCFXG_E_ARG;
-    if (!c->indexed || !c->fx_scanned) return VCFXG_E_STATE;
+    if (!c->indexed || !is_done(c, c->fx_scanned)) return VCFXG_E_STATE;
     if (first > c->n_lines || count > c->n_lines - first) return VCFXG_E_ARG;
     if (!count) return VCFXG_OK;
     int r = fx_fetch(c, c->fx_status, first, count, status);
@@ -178,7 +179,7 @@ int vcfxg_fields_lines(vcfxg_ctx *c, uint64_t first, uint64_t count, uint8_t *st
 
 int vcfxg_fields_cells(vcfxg_ctx *c, uint64_t first, uint64_t count, uint32_t *cells) {
     if (!c) return VCFXG_E_ARG;
-    if (!c->indexed || !c->fx_scanned) return VCFXG_E_STATE;
+    if (!c->indexed || !is_done(c, c->fx_scanned)) return VCFXG_E_STATE;
     if (first > c->n_lines || count > c->n_lines - first) return VCFXG_E_ARG;
     if (!count) return VCFXG_OK;
     if (!cells) return VCFXG_E_ARG;
@@ -190,7 +191,7 @@ int vcfxg_fields_cells(vcfxg_ctx *c, uint64_t first, uint64_t count, uint32_t *c
 
 int vcfxg_fields_text(vcfxg_ctx *c, vcfxg_summary *out) {
     if (!c) return VCFXG_E_ARG;
-    if (!c->indexed || !c->fx_scanned) return VCFXG_E_STATE;
+    if (!c->indexed || !is_done(c, c->fx_scanned)) return VCFXG_E_STATE;
     HIPCHK(c, hipSetDevice(c->device));
     if (out) std::memset(out, 0, sizeof *out);
     const int r = ensure(c, c->text, c->fx_text + 16);

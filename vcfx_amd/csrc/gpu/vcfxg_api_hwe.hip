@@ -12,7 +12,7 @@ extern "C" {
 // past the capacity are formatted again once it has grown.  A walker over its line capacity
 // reruns the call without the walk.
 static int hwe_region_impl(vcfxg_ctx *c, size_t data_start, int mode, vcfxg_summary *out, bool walk) {
-    if (c) c->dense_pending = false;  // a new index / regions replace the pending ones
+    new_index(c);
     HIPCHK(c, hipSetDevice(c->device));
     const WalkPlan pl = walk_plan(c, data_start);
     const int64_t lo = pl.lo;
@@ -36,7 +36,7 @@ static int hwe_region_impl(vcfxg_ctx *c, size_t data_start, int mode, vcfxg_summ
         r = vcfxg_index(c, data_start, &L);
         if (r) return r;
         cap = L;
-        r = af_buffers(c, cap);
+        r = af_buffers(c, cap, StatusOwner::other);
         if (!r) r = ensure(c, c->hwe_aux, 4 * (cap + 1));
         if (!r) r = ensure(c, c->hwe_rc, sizeof(vcfxg_hwe_recheck) * (cap + 1));
         if (r) return r;

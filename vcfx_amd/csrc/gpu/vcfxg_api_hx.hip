@@ -26,18 +26,18 @@ int vcfxg_haplotype_scan(vcfxg_ctx *c, const vcfxg_hx_params *p, vcfxg_summary *
     if (!c->indexed) return VCFXG_E_STATE;
     DENSE(c);
     HIPCHK(c, hipSetDevice(c->device));
-    c->hx_scanned = c->hx_laid = false;
-    c->dd_done = c->srt_done = c->df_done = c->mg_done = c->rs_done = c->ms_done = c->fa_scanned = false;  // (the statuses are this call's now)
+    claim_status(c, StatusOwner::haplotype);
+    c->hx_scanned = c->hx_laid = {};
     if (out) std::memset(out, 0, sizeof *out);
     const uint64_t n = c->n_lines, ns = p->n_samples;
     c->hx_ns = p->n_samples;
     c->hx_nm = c->hx_nb = 0;
     if (!n) {
-        c->hx_scanned = true;
+        mark_done(c, c->hx_scanned);
         return VCFXG_OK;
     }
     if (n > (~0ull / kHxCellBytes) / ns) return VCFXG_E_NOMEM;
-    int r = af_buffers(c, n);
+    int r = af_buffers(c, n, StatusOwner::haplotype);
     if (!r) r = ensure(c, c->hx_pos, 8 * n);
     if (!r) r = ensure(c, c->hx_flag, 4 * (n + 1));
     if (!r) r = ensure(c, c->hx_mnum, 8 * (n + 1));
@@ -97,7 +97,7 @@ int vcfxg_haplotype_scan(vcfxg_ctx *c, const vcfxg_hx_params *p, vcfxg_summary *
     prof_collect(c);
     c->hx_nm = nm;
     c->hx_nb = nb;
-    c->hx_scanned = true;
+    mark_done(c, c->hx_scanned);
     if (out) {
         out->n_lines = n;
         out->rows = nm;
@@ -110,7 +110,7 @@ int vcfxg_haplotype_scan(vcfxg_ctx *c, const vcfxg_hx_params *p, vcfxg_summary *
 int vcfxg_haplotype_lines(vcfxg_ctx *c, uint64_t first, uint64_t count, uint8_t *status, int64_t *pos, uint64_t *member,
                           uint64_t *block, uint32_t *flip) {
     if (!c) return VCFXG_E_ARG;
-    if (!c->indexed || !c->hx_scanned) return VCFXG_E_STATE;
+    if (!c->indexed || !is_done(c, c->hx_scanned) || (status && c->status_owner != StatusOwner::haplotype)) return VCFXG_E_STATE;
     if (first > c->n_lines || count > c->n_lines - first) return VCFXG_E_ARG;
     if (!count) return VCFXG_OK;
     int r = hx_fetch(c, c->status, first, count, status);
@@ -125,9 +125,9 @@ int vcfxg_haplotype_lines(vcfxg_ctx *c, uint64_t first, uint64_t count, uint8_t 
 
 int vcfxg_haplotype_blocks(vcfxg_ctx *c, vcfxg_summary *out) {
     if (!c) return VCFXG_E_ARG;
-    if (!c->indexed || !c->hx_scanned) return VCFXG_E_STATE;
+    if (!c->indexed || !is_done(c, c->hx_scanned)) return VCFXG_E_STATE;
     HIPCHK(c, hipSetDevice(c->device));
-    c->hx_laid = false;
+    c->hx_laid = {};
     if (out) std::memset(out, 0, sizeof *out);
     const uint64_t nm = c->hx_nm, nb = c->hx_nb, ns = c->hx_ns, nt = hx_tiles(nm);
     c->hx_text = 0;
@@ -161,7 +161,7 @@ int vcfxg_haplotype_blocks(vcfxg_ctx *c, vcfxg_summary *out) {
         c->hx_text = tail;
     }
     prof_collect(c);
-    c->hx_laid = true;
+    mark_done(c, c->hx_laid);
     if (out) {
         out->n_lines = c->n_lines;
         out->rows = nb;
@@ -174,7 +174,7 @@ int vcfxg_haplotype_blocks(vcfxg_ctx *c, vcfxg_summary *out) {
 int vcfxg_haplotype_table(vcfxg_ctx *c, uint64_t first, uint64_t count, uint64_t *first_member, uint64_t *last_member,
                           int64_t *start, int64_t *end, uint64_t *row_off, uint64_t *row_len) {
     if (!c) return VCFXG_E_ARG;
-    if (!c->indexed || !c->hx_scanned || !c->hx_laid) return VCFXG_E_STATE;
+    if (!c->indexed || !is_done(c, c->hx_scanned) || !is_done(c, c->hx_laid)) return VCFXG_E_STATE;
     if (first > c->hx_nb || count > c->hx_nb - first) return VCFXG_E_ARG;
     if (!count) return VCFXG_OK;
     int r = hx_fetch(c, c->hx_first, first, count, first_member);
@@ -190,7 +190,7 @@ int vcfxg_haplotype_table(vcfxg_ctx *c, uint64_t first, uint64_t count, uint64_t
 
 int vcfxg_haplotype_text(vcfxg_ctx *c, vcfxg_summary *out) {
     if (!c) return VCFXG_E_ARG;
-    if (!c->indexed || !c->hx_scanned || !c->hx_laid) return VCFXG_E_STATE;
+    if (!c->indexed || !is_done(c, c->hx_scanned) || !is_done(c, c->hx_laid)) return VCFXG_E_STATE;
     HIPCHK(c, hipSetDevice(c->device));
     if (out) std::memset(out, 0, sizeof *out);
     const uint64_t nm = c->hx_nm, nb = c->hx_nb;

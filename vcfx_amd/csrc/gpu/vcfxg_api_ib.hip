@@ -14,7 +14,7 @@ extern "C" {
 // overflow flag, the counts, the text size); a walker overflow repeats the call on the index.
 static int ib_region_impl(vcfxg_ctx *c, size_t data_start, int mode, const vcfxg_ib_params *p, vcfxg_summary *out,
                           bool walk) {
-    c->dense_pending = false;
+    new_index(c);
     HIPCHK(c, hipSetDevice(c->device));
     const WalkPlan pl = walk_plan(c, data_start);  // (k_ib_walk packs no 16-bit count: no fits_gt16 check)
     const int64_t lo = pl.lo, hi = pl.hi, C = pl.C, nw = pl.nw;

@@ -81,9 +81,9 @@ int text_block(vcfxg_ctx *c, TextOrder &T, const char *src_text, uint64_t first,
     return VCFXG_OK;
 }
 
-int fetch_status(vcfxg_ctx *c, bool done, uint64_t first, uint64_t count, uint8_t *status) {
+int fetch_status(vcfxg_ctx *c, StatusOwner owner, const Done &done, uint64_t first, uint64_t count, uint8_t *status) {
     if (!status && count) return VCFXG_E_ARG;
-    if (!c->indexed || !done) return VCFXG_E_STATE;
+    if (!c->indexed || !is_done(c, done) || c->status_owner != owner) return VCFXG_E_STATE;
     if (first > c->n_lines || count > c->n_lines - first) return VCFXG_E_ARG;
     if (!count) return VCFXG_OK;
     HIPCHK(c, hipSetDevice(c->device));
@@ -92,9 +92,9 @@ int fetch_status(vcfxg_ctx *c, bool done, uint64_t first, uint64_t count, uint8_
     return VCFXG_OK;
 }
 
-int fetch_order(vcfxg_ctx *c, bool done, const uint32_t *order, uint64_t n, uint64_t first, uint64_t count, uint32_t *lines) {
+int fetch_order(vcfxg_ctx *c, const Done &done, const uint32_t *order, uint64_t n, uint64_t first, uint64_t count, uint32_t *lines) {
     if (!lines && count) return VCFXG_E_ARG;
-    if (!c->indexed || !done) return VCFXG_E_STATE;
+    if (!c->indexed || !is_done(c, done)) return VCFXG_E_STATE;
     if (first > n || count > n - first) return VCFXG_E_ARG;
     if (!count) return VCFXG_OK;
     HIPCHK(c, hipSetDevice(c->device));

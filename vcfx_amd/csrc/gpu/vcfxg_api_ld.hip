@@ -233,7 +233,7 @@ int vcfxg_ld_prepare_region(vcfxg_ctx *c, size_t data_start, int n_samples, int 
     if (!c || n_samples < 0 || (has_region && !rchrom && rlen)) return VCFXG_E_ARG;
     if (!c->loaded) return VCFXG_E_STATE;
     if (data_start > c->n) data_start = c->n;
-    c->dense_pending = false;  // a new index / regions replace the pending ones
+    new_index(c);
     HIPCHK(c, hipSetDevice(c->device));
     static const bool walk_env = [] {
         const char *e = getenv("VCFXG_LD_WALK");

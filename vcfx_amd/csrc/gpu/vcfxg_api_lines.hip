@@ -75,7 +75,7 @@ int vcfxg_allele_counter(vcfxg_ctx *c, uint64_t l0, uint64_t l1, const vcfxg_ac_
         } else
             r = rd;
     }
-    if (!r) r = af_buffers(c, L);
+    if (!r) r = af_buffers(c, L, StatusOwner::other);
     if (!r) r = ensure(c, c->af_meta, vcfxg::ac_meta_bytes() * (L + 1));
     if (r) return r;
     HIPCHK(c, hipMemcpyAsync(c->ac_eff.p, c->ac_eff_host.data(), 4 * (m + 1), hipMemcpyHostToDevice, c->stream));
@@ -157,7 +157,7 @@ int vcfxg_sample_extract(vcfxg_ctx *c, uint64_t l0, uint64_t l1, const vcfxg_sx_
     c->sx_mask_host[0] = 0x1FFu;
     for (uint32_t i = 0; i < m; i++) c->sx_mask_host[p->cols[i] >> 5] |= 1u << (p->cols[i] & 31u);
     int r = ensure(c, c->sx_mask, 4 * ((size_t)nwords + 2));
-    if (!r) r = af_buffers(c, L);
+    if (!r) r = af_buffers(c, L, StatusOwner::other);
     if (r) return r;
     HIPCHK(c, hipMemcpyAsync(c->sx_mask.p, c->sx_mask_host.data(), 4 * ((size_t)nwords + 2), hipMemcpyHostToDevice,
                              c->stream));

@@ -30,7 +30,8 @@ int vcfxg_merge(vcfxg_ctx *c, const vcfxg_mg_params *p, vcfxg_summary *out) {
     const uint64_t L = c->n_lines;
     if (L >= (1ull << 31)) return VCFXG_E_ARG;  // (the scans and the sort count their items in an int)
     HIPCHK(c, hipSetDevice(c->device));
-    c->mg_done = false;
+    claim_status(c, StatusOwner::merge);
+    c->mg_done = {};
     c->mg_out.n = 0;
     c->mg_out.off_host.clear();
     c->mg_files = K;
@@ -40,7 +41,7 @@ int vcfxg_merge(vcfxg_ctx *c, const vcfxg_mg_params *p, vcfxg_summary *out) {
     c->mg_counts[7] = K;
     if (out) std::memset(out, 0, sizeof *out);
     const uint64_t K1 = (uint64_t)K + 1;
-    int r = ensure(c, c->status, L + 1);
+    int r = status_buffer(c, L, StatusOwner::merge);
     if (!r) r = ensure(c, c->counters, 128);
     if (!r) r = ensure(c, c->mg_fmeta, 8 * 7 * K1);
     if (!r) r = ensure(c, c->mg_file, 4 * (L + 1));
@@ -75,7 +76,7 @@ int vcfxg_merge(vcfxg_ctx *c, const vcfxg_mg_params *p, vcfxg_summary *out) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         prof_end(c, "mg_key");
         prof_collect(c);
-        c->mg_done = true;
+        mark_done(c, c->mg_done);
         return VCFXG_OK;
     }
     HIPCHK(c, hipMemsetAsync(written + L, 0, 4, c->stream));
@@ -141,7 +142,7 @@ int vcfxg_merge(vcfxg_ctx *c, const vcfxg_mg_params *p, vcfxg_summary *out) {
         prof_end(c, "mg_order");
     }
     prof_collect(c);
-    c->mg_done = true;
+    mark_done(c, c->mg_done);
     if (out) {
         out->n_lines = L;
         out->rows = nw;
@@ -153,19 +154,19 @@ int vcfxg_merge(vcfxg_ctx *c, const vcfxg_mg_params *p, vcfxg_summary *out) {
 }
 
 int vcfxg_merge_status(vcfxg_ctx *c, uint64_t first, uint64_t count, uint8_t *status) {
-    return c ? fetch_status(c, c->mg_done, first, count, status) : VCFXG_E_ARG;
+    return c ? fetch_status(c, StatusOwner::merge, c->mg_done, first, count, status) : VCFXG_E_ARG;
 }
 
 int vcfxg_merge_counts(const vcfxg_ctx *c, uint64_t counts[8]) {
     if (!c || !counts) return VCFXG_E_ARG;
-    if (!c->indexed || !c->mg_done) return VCFXG_E_STATE;
+    if (!c->indexed || !is_done(c, c->mg_done)) return VCFXG_E_STATE;
     std::memcpy(counts, c->mg_counts, sizeof c->mg_counts);
     return VCFXG_OK;
 }
 
 int vcfxg_merge_files(vcfxg_ctx *c, uint64_t *first_line, uint64_t *bad) {
     if (!c || !first_line || !bad) return VCFXG_E_ARG;
-    if (!c->indexed || !c->mg_done) return VCFXG_E_STATE;
+    if (!c->indexed || !is_done(c, c->mg_done)) return VCFXG_E_STATE;
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t K1 = (uint64_t)c->mg_files + 1;
     const uint64_t *fm = P<uint64_t>(c->mg_fmeta);
@@ -184,7 +185,7 @@ int vcfxg_merge_text(vcfxg_ctx *c, uint64_t first, uint64_t *lines_taken, uint64
     if (!c) return VCFXG_E_ARG;
     if (lines_taken) *lines_taken = 0;
     if (bytes) *bytes = 0;
-    if (!c->indexed || !c->mg_done) return VCFXG_E_STATE;
+    if (!c->indexed || !is_done(c, c->mg_done)) return VCFXG_E_STATE;
     if (first > c->mg_out.n) return VCFXG_E_ARG;
     return text_block(c, c->mg_out, P<char>(c->input), first, c->mg_out.n, c->srt_block, "mg_gather", lines_taken, bytes);
 }

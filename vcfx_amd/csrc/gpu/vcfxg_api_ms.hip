@@ -55,15 +55,14 @@ int vcfxg_multiallelic_split(vcfxg_ctx *c, uint64_t l0, uint64_t l1, const vcfxg
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t n = l1 - l0, L = c->n_lines;
     c->text_bytes = 0;
-    c->ms_done = false;
-    c->dd_done = false;  // (the statuses are this call's now)
+    c->ms_done = {};
     if (out) std::memset(out, 0, sizeof *out);
     if (!n) return VCFXG_OK;
     const uint32_t ne = ms_build_table(p, c->ms_tab_host);
     const size_t tb = 4 * (c->ms_tab_host.size() - 1);
     if (tb >= (1ull << 31)) return VCFXG_E_ARG;
     int r = ensure(c, c->ms_tab, tb + 4);
-    if (!r) r = af_buffers(c, L);
+    if (!r) r = af_buffers(c, L, StatusOwner::other);
     if (!r) r = ensure(c, c->ms_geom, 4 * (size_t)kMsGeom * n);
     if (!r) r = ensure(c, c->ms_cost, 8 * (n + 1));
     if (!r) r = ensure(c, c->ms_costoff, 8 * (n + 1));
@@ -123,7 +122,7 @@ int vcfxg_multiallelic_split(vcfxg_ctx *c, uint64_t l0, uint64_t l1, const vcfxg
     c->text_bytes = text;
     c->ms_l0 = l0;
     c->ms_n = taken;
-    c->ms_done = true;
+    mark_done(c, c->ms_done);
     if (out) {
         out->n_lines = taken;
         out->rows = rows;
@@ -136,7 +135,7 @@ int vcfxg_multiallelic_split(vcfxg_ctx *c, uint64_t l0, uint64_t l1, const vcfxg
 
 int vcfxg_ms_line_ranges(vcfxg_ctx *c, uint64_t first, uint64_t count, uint64_t *off) {
     if (!c || !off) return VCFXG_E_ARG;
-    if (!c->indexed || !c->ms_done) return VCFXG_E_STATE;
+    if (!c->indexed || !is_done(c, c->ms_done)) return VCFXG_E_STATE;
     if (first < c->ms_l0 || first + count > c->ms_l0 + c->ms_n) return VCFXG_E_ARG;
     HIPCHK(c, hipMemcpyAsync(off, P<uint64_t>(c->ms_lineoff) + (first - c->ms_l0), 8 * (count + 1), hipMemcpyDeviceToHost,
                              c->stream));

@@ -23,7 +23,7 @@ int vcfxg_regions_load(vcfxg_ctx *c, const char *names, const uint64_t *name_off
         if (chrom_id[j] >= n_chrom || start1[j] < 1 || end[j] < start1[j]) return VCFXG_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     c->rs_loaded = false;
-    c->rs_done = false;  // (statuses of an earlier filter belong to the table they were made with)
+    c->rs_done = {};  // (statuses of an earlier filter belong to the table they were made with)
     const uint64_t name_bytes = n_chrom ? name_off[n_chrom] : 0;
     uint32_t slots = 4;
     while (slots < 2u * n_chrom) slots <<= 1;
@@ -127,14 +127,15 @@ int vcfxg_region_filter(vcfxg_ctx *c, int mode, vcfxg_summary *out) {
     const uint64_t L = c->n_lines;
     if (L >= (1ull << 31)) return VCFXG_E_ARG;  // (the wave list holds line numbers in 32 bits)
     HIPCHK(c, hipSetDevice(c->device));
-    c->rs_done = false;
+    claim_status(c, StatusOwner::region);
+    c->rs_done = {};
     std::memset(c->rs_counts, 0, sizeof c->rs_counts);
     if (out) std::memset(out, 0, sizeof *out);
     if (!L) {
-        c->rs_done = true;
+        mark_done(c, c->rs_done);
         return VCFXG_OK;
     }
-    int r = ensure(c, c->status, L + 1);
+    int r = status_buffer(c, L, StatusOwner::region);
     if (!r) r = ensure(c, c->counters, 128);
     if (!r) r = ensure(c, c->rs_queue, 4 * L);
     if (r) return r;
@@ -153,7 +154,7 @@ int vcfxg_region_filter(vcfxg_ctx *c, int mode, vcfxg_summary *out) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
     for (int i = 0; i < 8; i++) c->rs_counts[i] = cnt[i];
-    c->rs_done = true;
+    mark_done(c, c->rs_done);
     if (out) {
         out->n_lines = L;
         out->rows = cnt[VCFXG_RS_IN];
@@ -165,7 +166,7 @@ int vcfxg_region_filter(vcfxg_ctx *c, int mode, vcfxg_summary *out) {
 }
 
 int vcfxg_region_status(vcfxg_ctx *c, uint64_t first, uint64_t count, uint8_t *status) {
-    return c ? fetch_status(c, c->rs_done, first, count, status) : VCFXG_E_ARG;
+    return c ? fetch_status(c, StatusOwner::region, c->rs_done, first, count, status) : VCFXG_E_ARG;
 }
 
 int vcfxg_region_counts(const vcfxg_ctx *c, uint64_t counts[8]) {

@@ -22,16 +22,17 @@ int vcfxg_sort(vcfxg_ctx *c, int mode, const vcfxg_srt_params *p, vcfxg_summary 
     const uint64_t L = c->n_lines;
     if (L >= (1ull << 31)) return VCFXG_E_ARG;  // (the scans and the sort count their items in an int)
     HIPCHK(c, hipSetDevice(c->device));
-    c->srt_done = false;
+    claim_status(c, StatusOwner::sort);
+    c->srt_done = {};
     c->srt_out.n = 0;
     c->srt_out.off_host.clear();
     std::memset(c->srt_counts, 0, sizeof c->srt_counts);
     if (out) std::memset(out, 0, sizeof *out);
     if (!L) {
-        c->srt_done = true;
+        mark_done(c, c->srt_done);
         return VCFXG_OK;
     }
-    int r = ensure(c, c->status, L + 1);
+    int r = status_buffer(c, L, StatusOwner::sort);
     if (!r) r = ensure(c, c->counters, 64);
     if (!r) r = ensure(c, c->srt_pos, 4 * L);
     if (!r) r = ensure(c, c->srt_aux, 4 * L);
@@ -92,7 +93,7 @@ int vcfxg_sort(vcfxg_ctx *c, int mode, const vcfxg_srt_params *p, vcfxg_summary 
         prof_end(c, "srt_sort");
     }
     prof_collect(c);
-    c->srt_done = true;
+    mark_done(c, c->srt_done);
     if (out) {
         out->n_lines = L;
         out->rows = nw;
@@ -104,7 +105,7 @@ int vcfxg_sort(vcfxg_ctx *c, int mode, const vcfxg_srt_params *p, vcfxg_summary 
 }
 
 int vcfxg_sort_status(vcfxg_ctx *c, uint64_t first, uint64_t count, uint8_t *status) {
-    return c ? fetch_status(c, c->srt_done, first, count, status) : VCFXG_E_ARG;
+    return c ? fetch_status(c, StatusOwner::sort, c->srt_done, first, count, status) : VCFXG_E_ARG;
 }
 
 int vcfxg_sort_counts(const vcfxg_ctx *c, uint64_t counts[6]) {
@@ -122,7 +123,7 @@ int vcfxg_sort_text(vcfxg_ctx *c, uint64_t first, uint64_t *lines_taken, uint64_
     if (!c) return VCFXG_E_ARG;
     if (lines_taken) *lines_taken = 0;
     if (bytes) *bytes = 0;
-    if (!c->indexed || !c->srt_done) return VCFXG_E_STATE;
+    if (!c->indexed || !is_done(c, c->srt_done)) return VCFXG_E_STATE;
     if (first > c->srt_out.n) return VCFXG_E_ARG;
     return text_block(c, c->srt_out, P<char>(c->input), first, c->srt_out.n, c->srt_block, "srt_gather", lines_taken, bytes);
 }

@@ -115,11 +115,16 @@ bool walk_wanted(const vcfxg_ctx *c, bool need_gt_only) {
 
 bool af_knob_allows_walk(const vcfxg_ctx *c) { return c->af_path != 3 && c->af_path != 8; }
 
-int af_buffers(vcfxg_ctx *c, uint64_t L) {
+int status_buffer(vcfxg_ctx *c, uint64_t L, StatusOwner owner) {
+    claim_status(c, owner);
+    return ensure(c, c->status, L + 1);
+}
+
+int af_buffers(vcfxg_ctx *c, uint64_t L, StatusOwner owner) {
     int r = ensure(c, c->alt, 4 * (L + 1));
     if (!r) r = ensure(c, c->tot, 4 * (L + 1));
     if (!r) r = ensure(c, c->rowpre, 4 * (L + 1));
-    if (!r) r = ensure(c, c->status, L + 1);
+    if (!r) r = status_buffer(c, L, owner);
     if (!r) r = ensure(c, c->rowlen, 8 * (L + 1));
     if (!r) r = ensure(c, c->rowoff, 8 * (L + 1));
     return r;
@@ -152,7 +157,7 @@ int walk_buffers(vcfxg_ctx *c, const WalkPlan &p) {
 // the dense per-line arrays the regions are compacted into, for up to L lines
 int dense_buffers(vcfxg_ctx *c, uint64_t L) {
     int r = ensure(c, c->line_end, 8 * (L + 1));
-    if (!r) r = af_buffers(c, L);
+    if (!r) r = af_buffers(c, L, StatusOwner::other);
     if (!r) r = ensure(c, c->af_meta, af_meta_bytes() * (L + 1));
     return r;
 }
@@ -226,7 +231,7 @@ int fq_walk_to_dense(vcfxg_ctx *c, const WalkPlan &p, int what, int strip_cr, co
     if (!r) r = ensure(c, c->wk_offs, 8 * (size_t)(p.nw + 1));
     if (!r) r = ensure(c, c->fq_small, 128);
     if (!r) r = ensure(c, c->line_end, 8 * (p.cap + 1));
-    if (!r) r = ensure(c, c->status, p.cap + 1);
+    if (!r) r = status_buffer(c, p.cap, StatusOwner::other);
     if (!r && meta) r = ensure(c, c->af_meta, mb * (p.cap + 1));
     if (!r) r = ensure_sum_host(c);
     if (r) return r;

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -13,16 +14,48 @@
 #include <vector>
 
 #include "vcfx_gpu.h"
+#include "vcfxg_env.h"
 #include "vcfxg_kernels.h"
 #include "vcfxg_rf.h"
 
+// A device allocation that frees itself (non-copyable, movable).  alloc and release are the only places
+// that call hipMalloc / hipFree for a buffer, and the only ones that change `live`, the capacities that
+// the DevBufs of the process hold (vcfxg_device_bytes_live).
 struct DevBuf {
+    static inline std::atomic<uint64_t> live{0};
     void *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept {  // (what this held goes to o, and is freed with it)
+        std::swap(p, o.p), std::swap(cap, o.cap);
+        return *this;
+    }
+    ~DevBuf() { (void)release(); }
+    hipError_t alloc(size_t bytes) {  // for an empty buffer, which stays empty when the device has none
+        void *np = nullptr;
+        const hipError_t e = hipMalloc(&np, bytes);
+        if (e == hipSuccess) p = np, cap = bytes, live += bytes;
+        return e;
+    }
+    hipError_t release() {  // empty afterwards, whatever hipFree says (the caller has waited for readers)
+        const hipError_t e = p ? hipFree(p) : hipSuccess;
+        live -= cap;
+        p = nullptr, cap = 0;
+        return e;
+    }
 };
 
-// The stages the keyed line tools share (vcfxg_api_keyed.hip).  Every tool owns its instances: one
-// tool's results stay readable after another tool ran on the context.
+// Whose per-line statuses c->status holds.  Every call that writes the buffer claims it first
+// (claim_status); a status fetch is served only to the owner.
+enum class StatusOwner { none, other, dedup, sort, diff, merge, region, fasta, haplotype };
+// "This call has run on the current index": the index generation (vcfxg_ctx::index_gen) it completed
+// on; a new index outdates every tool's results at once (mark_done / is_done below; = {} withdraws).
+struct Done { uint64_t gen = 0; };
+
+// The stages the keyed line tools share (vcfxg_api_keyed.hip).  Every tool owns its instances, so
+// its orders, counts and texts stay readable after another tool ran on the context; the per-line
+// status buffer is the context's one, and holds the last writer's statuses only (StatusOwner).
 // A stable radix sort of (64-bit key part, line) pairs, pass after pass: (ka, va) holds the pairs to
 // sort, and after a pass the sorted ones; va is the order so far.
 struct SortScratch {
@@ -58,8 +91,10 @@ struct vcfxg_ctx {
     size_t data_start = 0;
     uint64_t n_lines = 0;
     bool indexed = false;
+    uint64_t index_gen = 1;  // bumped wherever a new index replaces the old one (new_index)
     // per-line results
     DevBuf alt, tot, rowpre, status, rowlen, rowoff, text, counters, query, crit, pool;
+    StatusOwner status_owner = StatusOwner::none;
     std::string query_host, crit_host, pool_host;  // host sources of in-flight async copies
     // LD
     DevBuf ld_G, ld_lines, ld_vidx, ld_valid, ld_Gc, ld_vars, ld_plen, ld_poff, ld_prefix, ld_cid, ld_blocks, ld_cnt,
@@ -89,7 +124,7 @@ struct vcfxg_ctx {
     DevBuf ld_temp, ld_quarters, ld_stage_ctr;  // LD: pairs staged by the count pass
     uint64_t ld_temp_cap = 0;
     // test hook: a fixed (small) staging capacity exercises the overflow -> emit-pass path
-    uint64_t ld_stage_cap_fixed = getenv("VCFXG_LD_STAGE_CAP") ? strtoull(getenv("VCFXG_LD_STAGE_CAP"), nullptr, 10) : 0;
+    uint64_t ld_stage_cap_fixed = vcfxg::env_u64("VCFXG_LD_STAGE_CAP", 0);
     DevBuf af_meta;             // AF head pass output (k_af_meta)
     // walk AF path (vcfxg_af_walk.hip): per-walker regions, counts, scan, flags
     DevBuf wk_le, wk_alt, wk_tot, wk_rowpre, wk_status, wk_meta, wk_count, wk_offs, wk_gt, wk_small;
@@ -137,9 +172,7 @@ struct vcfxg_ctx {
     // tests make many blocks, and blocks of one line, with small values)
     DevBuf sx_mask;
     std::vector<uint32_t> sx_mask_host;
-    uint64_t sx_block = getenv("VCFXG_SX_BLOCK")
-                            ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_SX_BLOCK"), nullptr, 10), 1), 1u << 24)
-                            : 65536;
+    uint64_t sx_block = vcfxg::env_u64("VCFXG_SX_BLOCK", 65536, 1, 1u << 24);
     // VCFX_cross_sample_concordance: column multiplicities, data-line flags and their scan, the
     // "#CHROM" line list, the summary words; the last call's totals
     DevBuf cc_mult, cc_isdata, cc_ord, cc_chrom, cc_small;
@@ -151,7 +184,7 @@ struct vcfxg_ctx {
     DevBuf dd_tabs, dd_pos, dd_hash, dd_queue, dd_isdata, dd_ord, dd_hp, dd_head, dd_left;
     SortScratch dd_sort;
     uint64_t dd_counts[6] = {0, 0, 0, 0, 0, 0};
-    bool dd_done = false;  // c->status holds the last vcfxg_dedup's statuses (of this index)
+    Done dd_done;  // vcfxg_dedup has run on this index (its statuses: while status_owner says so)
     // VCFX_sorter: per line POS, aux (chromToId or CHROM's length) and CHROM's first word, the wave
     // pass's line list, the written flags and their scan; the sort of the (key, line) pairs
     // (srt_sort.va: the order); the output lines (srt_out.n of them); the last call's counts per
@@ -163,11 +196,9 @@ struct vcfxg_ctx {
     SortScratch srt_sort;
     TextOrder srt_out;
     uint64_t srt_counts[6] = {0, 0, 0, 0, 0, 0};
-    bool srt_done = false;
-    uint64_t srt_block = getenv("VCFXG_SRT_BLOCK")
-                             ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_SRT_BLOCK"), nullptr, 10), 1), 1ull << 36)
-                             : 256ull << 20;
-    int srt_nt = getenv("VCFXG_SRT_NT") ? atoi(getenv("VCFXG_SRT_NT")) & 3 : 3;
+    Done srt_done;
+    uint64_t srt_block = vcfxg::env_u64("VCFXG_SRT_BLOCK", 256ull << 20, 1, 1ull << 36);
+    int srt_nt = (int)vcfxg::env_i64("VCFXG_SRT_NT", 3) & 3;
     // VCFX_diff_tool: per line the five tab offsets, the key's length and its scan, ALT's token count,
     // POS and CHROM's natural-order parts, the key's hash, the data flags and their scan, the wave
     // passes' line list; the key text; the data lines in line order; the sort of the (hash, line)
@@ -182,13 +213,9 @@ struct vcfxg_ctx {
     TextOrder df_out;
     uint64_t df_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t df_nu1 = 0;
-    bool df_done = false;
-    uint64_t df_block = getenv("VCFXG_DF_BLOCK")
-                            ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_DF_BLOCK"), nullptr, 10), 1), 1ull << 36)
-                            : 256ull << 20;
-    uint64_t df_walk_steps = getenv("VCFXG_DF_WALK_STEPS")
-                                 ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_DF_WALK_STEPS"), nullptr, 10), 1), 1ull << 24)
-                                 : 1ull << 20;
+    Done df_done;
+    uint64_t df_block = vcfxg::env_u64("VCFXG_DF_BLOCK", 256ull << 20, 1, 1ull << 36);
+    uint64_t df_walk_steps = vcfxg::env_u64("VCFXG_DF_WALK_STEPS", 1ull << 20, 1, 1ull << 24);
     // VCFX_merger: per line its file, POS and the key string's descriptor (first word, start, length;
     // with -n the prefix word and the digit run's value), the wave pass's line list, the written
     // flags and their scan; per file (K + 1 words each) its first byte, first line, first '#' line,
@@ -202,10 +229,8 @@ struct vcfxg_ctx {
     TextOrder mg_out;
     uint64_t mg_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t mg_files = 0;
-    bool mg_done = false;
-    uint64_t mg_walk_steps = getenv("VCFXG_MG_WALK_STEPS")
-                                 ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_MG_WALK_STEPS"), nullptr, 10), 1), 1ull << 24)
-                                 : 1ull << 20;
+    Done mg_done;
+    uint64_t mg_walk_steps = vcfxg::env_u64("VCFXG_MG_WALK_STEPS", 1ull << 20, 1, 1ull << 24);
     // VCFX_region_subsampler: the table of the last vcfxg_regions_load (it outlives loads and indexes of
     // the input): its descriptor (RsTableArgs), the names' bytes and offsets, the dictionary, the uploaded intervals (ids, starts,
     // ends: 3 n words), their sort, the sorted ids and starts, the scan keys and tile maxima, the reach,
@@ -218,7 +243,7 @@ struct vcfxg_ctx {
     uint32_t rs_nchrom = 0;
     uint64_t rs_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     bool rs_loaded = false;  // a table is resident
-    bool rs_done = false;    // c->status holds the last vcfxg_region_filter's statuses (of this index)
+    Done rs_done;            // vcfxg_region_filter has run on this index (with this table)
     // VCFX_haplotype_extractor: per line POS, member flag and its scan, CHROM's length, the fixed-stride region's
     // offset, the matrix-row flag and its scan, member / block / flip;
     // the cell matrix (lines x samples); member -> line, block-start flags and their scan, flips; per block
@@ -229,7 +254,7 @@ struct vcfxg_ctx {
         hx_first, hx_last, hx_bstart, hx_bend, hx_head, hx_rowlen, hx_rowoff, hx_agg, hx_carry, hx_tstart, hx_base;
     uint64_t hx_nm = 0, hx_nb = 0, hx_text = 0;
     uint32_t hx_ns = 0;
-    bool hx_scanned = false, hx_laid = false;
+    Done hx_scanned, hx_laid;
     // VCFX_field_extractor: the table of the last vcfxg_fields_load (it outlives loads and indexes of the
     // input) and its counts; per line the status, the row flag and its scan, the row bytes and their scan, the cell
     // matrix (lines x columns), the requested sample columns' spans and the sub-fields' FORMAT indices (the
@@ -241,33 +266,26 @@ struct vcfxg_ctx {
     uint32_t fx_ncols = 0, fx_nsc = 0, fx_nsub = 0;
     uint64_t fx_rows = 0, fx_text = 0;
     bool fx_loaded = false;   // a table is resident
-    bool fx_scanned = false;  // the statuses and the matrix are the last vcfxg_fields_scan's (of this index and table)
+    Done fx_scanned;          // the statuses and the matrix are the last vcfxg_fields_scan's (of this index and table)
     // VCFX_multiallelic_splitter: the table; per line of the block its tab offsets, cost and the
     // scans of nAlts and cost; each line's text offset; {lines taken, rows}; the last call's block;
     // lines and text bytes per call (read when the context opens; tests make blocks of one line)
     DevBuf ms_tab, ms_geom, ms_cost, ms_costoff, ms_rowbase, ms_lineoff, ms_small;
     std::vector<uint32_t> ms_tab_host;
     uint64_t ms_l0 = 0, ms_n = 0;
-    bool ms_done = false;
-    uint64_t ms_block = getenv("VCFXG_MS_BLOCK")
-                            ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_MS_BLOCK"), nullptr, 10), 1), 1u << 24)
-                            : 65536;
+    Done ms_done;
+    uint64_t ms_block = vcfxg::env_u64("VCFXG_MS_BLOCK", 65536, 1, 1u << 24);
     // VCFX_fasta_converter: per line of the block its column flag, column number and FaMeta; the
     // block's base matrix; the rows' text offsets and skipped columns; the last scan's block; the
     // text is sized by vcfxg_fasta_begin; lines per call (read when the context opens; tests end
     // blocks in the middle of a FASTA line with 1 and 7)
     DevBuf fa_flag, fa_col, fa_meta, fa_M, fa_rowoff, fa_skip;
     uint64_t fa_l0 = 0, fa_n = 0, fa_cols = 0, fa_text = 0;
-    bool fa_scanned = false, fa_begun = false;
-    uint64_t fa_block = getenv("VCFXG_FA_BLOCK")
-                            ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_FA_BLOCK"), nullptr, 10), 1), 1u << 24)
-                            : 65536;
-    uint64_t ms_bytes = getenv("VCFXG_MS_BYTES") ? std::max<uint64_t>(strtoull(getenv("VCFXG_MS_BYTES"), nullptr, 10), 1)
-                                                 : 512ull << 20;
+    Done fa_scanned, fa_begun;
+    uint64_t fa_block = vcfxg::env_u64("VCFXG_FA_BLOCK", 65536, 1, 1u << 24);
+    uint64_t ms_bytes = vcfxg::env_u64("VCFXG_MS_BYTES", 512ull << 20, 1);
     // records per chain block (read when the context opens; tests cross block edges with 1, 7, 64)
-    uint64_t ib_block = getenv("VCFXG_IB_BLOCK")
-                            ? std::min<uint64_t>(std::max<uint64_t>(strtoull(getenv("VCFXG_IB_BLOCK"), nullptr, 10), 1), 1u << 24)
-                            : 65536;
+    uint64_t ib_block = vcfxg::env_u64("VCFXG_IB_BLOCK", 65536, 1, 1u << 24);
     // ulps either side of the device p-value that must print the same digits (test hook: a
     // huge value sends every exp()-derived row to the host).  How near the p-values come to a
     // value where the six-digit text changes, with the C library's exp (a CPU search over whole
@@ -275,13 +293,12 @@ struct vcfxg_ctx {
     // over every triple with N <= 100 (file mode, (2, 9, 5)); at N = 97 / 301 / 2504 it is
     // 10,520,075 / 1,906,818 / 134,905 ulps in file mode and 8,177,671 / 7,635,856 / 263,560 on
     // stdin.  tests/test_gpu_count_edges.py runs those triples: the device left none to the host.
-    int64_t hwe_ulps = getenv("VCFXG_HWE_ULPS") ? atoll(getenv("VCFXG_HWE_ULPS")) : 16;
+    int64_t hwe_ulps = vcfxg::env_i64("VCFXG_HWE_ULPS", 16);
     // (an override is clamped to [4 KiB, 8 MiB]: the AF walk packs a walker's GT-line count in
     // 16 bits, and its line capacity 2 * chunk / hint_line + 16 stays below 2^15 for the
     // >= 512 B records the walk takes)
-    int64_t walk_chunk = getenv("VCFXG_WALK_CHUNK")
-                             ? std::min<int64_t>(std::max<int64_t>(atol(getenv("VCFXG_WALK_CHUNK")), 4096), 8 << 20)
-                             : 128 * 1024;
+    int64_t walk_chunk = vcfxg::env_i64("VCFXG_WALK_CHUNK", 128 * 1024, 4096, 8 << 20);
+    const bool walk_chunk_forced = vcfxg::env_set("VCFXG_WALK_CHUNK");  // the hints leave it alone
     bool walk_overflowed = false;  // the last walk run overflowed: two-sweep schedule
     bool dose_head_failed = false;  // a dosage head walk's rows failed the check (this input)
     bool ph_head_failed = false;    // a phaser head-walk index failed the parse's check (this input)
@@ -296,33 +313,30 @@ struct vcfxg_ctx {
     bool hint_gt_first = false;
     uint64_t af_line_cap = 0;   // two-sweep AF: line capacity the last run needed
     // region AF schedule: 0 = default (the walk schedule 7 when the first records average
-    // >= 512 B, else 3 with one host synchronisation: single-sweep index + head pass +
-    // fixed-stride sweep), 1 = one-sweep look-back kernel (k_af_fused),
-    // 2 = chunk count + chunk sweep (k_af_chunks), 4 = one sweep with byte-class segment
-    // counts (k_af_scan); the single-sweep alternatives are correct and tested but slower
-    // today, kept selectable for measurement; 7 = walk (k_af_walk: predicted
-    // record ends validated by the sweep, one HBM pass); 8 = the two-sweep schedule always
-    int af_path = getenv("VCFXG_AF_FUSED") ? atoi(getenv("VCFXG_AF_FUSED")) : 0;
+    // >= 512 B, else 3), 3 = single-sweep index + head pass + fixed-stride sweep, with one host
+    // synchronisation; 7 = walk (k_af_walk: predicted record ends validated by the sweep, one HBM
+    // pass); 8 = the two-sweep schedule always
+    int af_path = (int)vcfxg::env_i64("VCFXG_AF_FUSED", 0);
     // the AF GT-only walk's sweep depth in wave-steps: 0 = the plan's choice (walk_plan), 6 / 8 /
     // 10 / 12 = that depth, rolling past it (tests, A/B); any other value is the plan's choice
-    int af_depth_knob = getenv("VCFXG_AF_DEPTH") ? atoi(getenv("VCFXG_AF_DEPTH")) : 0;
+    int af_depth_knob = (int)vcfxg::env_i64("VCFXG_AF_DEPTH", 0);
     int last_af_depth = 0;        // the depth / rolling of the last AF GT-only walk launched
     bool last_af_roll = false;    // (vcfxg_last_af_depth; 0: none yet)
     // the AF GT-only walk's chunk layout (walk_plan): VCFXG_WALK_LAYOUT = uniform | fit |
     // taper:<div>:<g> | split:<div>:<K1> (a test's explicit first short round), read when the context
     // opens; unset or anything else: the plan's default
-    vcfxg::WalkLayoutKnob walk_layout_knob = vcfxg::parse_walk_layout(getenv("VCFXG_WALK_LAYOUT"));
+    vcfxg::WalkLayoutKnob walk_layout_knob = vcfxg::parse_walk_layout(vcfxg::env_text("VCFXG_WALK_LAYOUT"));
     // the walkers resident at a time, per compiled (depth, roll) of the AF GT-only walk (queried once
     // each; 0: not yet); VCFXG_WALK_RESIDENT overrides the query (tests: a small device's layouts on
     // small inputs)
     mutable int64_t walk_resident[2][vcfxg::kAfDepthMax + 1] = {};
-    int64_t walk_resident_knob = getenv("VCFXG_WALK_RESIDENT") ? atoll(getenv("VCFXG_WALK_RESIDENT")) : 0;
+    int64_t walk_resident_knob = vcfxg::env_i64("VCFXG_WALK_RESIDENT", 0);
     vcfxg::WalkLayoutKnob last_walk_layout_kind;  // of the last AF GT-only walk launched
     vcfxg::WalkLayout last_walk_layout = {};      // (vcfxg_last_walk_layout)
     int64_t last_walk_resident = 0;
     // record_filter / genotype_query region schedule: 0 = the walk (vcfxg_fq_walk.hip) when
     // the first records average >= 512 B, 1 = the walk always, -1 = index + per-tool kernels
-    int fq_path = getenv("VCFXG_FQ_WALK") ? atoi(getenv("VCFXG_FQ_WALK")) : 0;
+    int fq_path = (int)vcfxg::env_i64("VCFXG_FQ_WALK", 0);
     std::vector<uint8_t> ld_gflag_host;  // per 128-variant group: all complete
     uint64_t ld_m = 0, ld_prefix_bytes = 0, ld_np = 0;
     int ld_kpad = 64, ld_ns = 0, ld_kp4 = 64;
@@ -366,6 +380,16 @@ namespace vcfxg {
 
 constexpr size_t kPad = 256;  // zeroed bytes after the input: 16 B loads may run past n
 
+// a new index (vcfxg_index's, or a region call's own): pending walker regions and every tool's results go
+inline void new_index(vcfxg_ctx *c) {
+    c->dense_pending = false;
+    c->index_gen++;
+}
+inline void mark_done(vcfxg_ctx *c, Done &d) { d.gen = c->index_gen; }
+inline bool is_done(const vcfxg_ctx *c, const Done &d) { return d.gen == c->index_gen; }
+// before a call's first launch that writes c->status
+inline void claim_status(vcfxg_ctx *c, StatusOwner owner) { c->status_owner = owner; }
+
 // ---- vcfxg_api.hip
 int fail(vcfxg_ctx *c, hipError_t e, const char *what);
 #define HIPCHK(ctx, x)                                          \
@@ -373,7 +397,9 @@ int fail(vcfxg_ctx *c, hipError_t e, const char *what);
         hipError_t e_ = (x);                                    \
         if (e_ != hipSuccess) return vcfxg::fail(ctx, e_, #x);  \
     } while (0)
-int ensure(vcfxg_ctx *c, DevBuf &b, size_t bytes);
+int ensure(vcfxg_ctx *c, DevBuf &b, size_t bytes);  // (b holds `bytes` at least; its old bytes are not kept)
+// b replaced by a fresh buffer of `bytes` that holds its first `keep` (the stream drained before the free)
+int regrow(vcfxg_ctx *c, DevBuf &b, size_t bytes, size_t keep);
 template <typename T>
 T *P(DevBuf &b) {
     return reinterpret_cast<T *>(b.p);
@@ -422,9 +448,10 @@ int place_lines(vcfxg_ctx *c, TextOrder &T, const uint64_t *line_end, int64_t da
 int text_block(vcfxg_ctx *c, TextOrder &T, const char *src_text, uint64_t first, uint64_t hi, uint64_t block,
                const char *region, uint64_t *taken, uint64_t *bytes);
 // the statuses of lines [first, first + count) of the index / entries [first, first + count) of an
-// order of n lines, to the host (done: the tool's call has run)
-int fetch_status(vcfxg_ctx *c, bool done, uint64_t first, uint64_t count, uint8_t *status);
-int fetch_order(vcfxg_ctx *c, bool done, const uint32_t *order, uint64_t n, uint64_t first, uint64_t count, uint32_t *lines);
+// order of n lines, to the host (done: the tool's call has run on this index; owner: the statuses
+// are served only while c->status is still that tool's, VCFXG_E_STATE otherwise)
+int fetch_status(vcfxg_ctx *c, StatusOwner owner, const Done &done, uint64_t first, uint64_t count, uint8_t *status);
+int fetch_order(vcfxg_ctx *c, const Done &done, const uint32_t *order, uint64_t n, uint64_t first, uint64_t count, uint32_t *lines);
 
 // ---- vcfxg_api_af.hip
 int ensure_dense(vcfxg_ctx *c);
@@ -436,7 +463,9 @@ int ensure_dense(vcfxg_ctx *c);
     } while (0)
 
 // ---- vcfxg_api_walk.hip: the record walks' plan, schedule predicates and shared sequences
-int af_buffers(vcfxg_ctx *c, uint64_t L);
+// c->status sized for L lines and claimed for `owner`; af_buffers: the other per-line buffers with it
+int status_buffer(vcfxg_ctx *c, uint64_t L, StatusOwner owner);
+int af_buffers(vcfxg_ctx *c, uint64_t L, StatusOwner owner);
 int ensure_sum_host(vcfxg_ctx *c);
 // the walkers of [data_start, n): chunk C (0: the context's walk_chunk), nw walkers of cap_w line
 // slots each, cap slots in all; fits_gt16: cap_w fits the 16-bit GT-line count k_af_walk packs

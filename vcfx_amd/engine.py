@@ -93,6 +93,7 @@ SIGNATURES = {
     "vcfxg_device_count": (_I, [ctypes.POINTER(_I)]),
     "vcfxg_open": (_I, [_I, ctypes.POINTER(_VP)]),
     "vcfxg_close": (None, [_VP]),
+    "vcfxg_device_bytes_live": (_U64, []),
     "vcfxg_last_error": (_P, [_VP]),
     "vcfxg_stream": (_VP, [_VP]),
     "vcfxg_set_profiling": (_I, [_VP, _I]),
@@ -218,6 +219,11 @@ def lib():
             f.restype = res
             f.argtypes = args
     return _lib
+
+
+def device_bytes_live():
+    """the device bytes the buffers of this process's open contexts hold (vcfxg_device_bytes_live)"""
+    return int(lib().vcfxg_device_bytes_live())
 
 
 class EngineError(RuntimeError):
